@@ -116,7 +116,39 @@ def parse_args(argv=None):
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="launcher/collective rehearsal WITHOUT a GPU: ranks rendezvous over gloo, shard, broadcast "
                          "a dummy spectrum and reduce a clock; no compute, value = null (CPU test of the N > 1 plumbing)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: larger outputs as a fixed, seeded sample of rows)")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SEED = 0xD0
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: [(name, array)], in order.  Each goes to out_dir/<name>.npy as float32 (float32 input) or float64 (anything
+    else, e.g. peak indices).  An array that does not fit what is left of the 64 MB budget is replaced by a seeded sample
+    of its rows (the same rows on every run) and the row indices go to <name>_rows.npy.  Returns {name: shape written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = DUMP_BUDGET_BYTES, {}
+    for name, a in arrays:
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        left -= 128                                                  # the .npy header
+        if a.nbytes > left:
+            row_bytes = a.nbytes // max(a.shape[0], 1) + 8           # a row + its index in <name>_rows.npy
+            n = min(a.shape[0], (left - 128) // row_bytes)
+            if n <= 0:
+                raise SystemExit(f"--dump-outputs: no room left for {name} within {DUMP_BUDGET_BYTES} bytes")
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], size=n, replace=False)).astype(np.float64)
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows)
+            left -= 128 + rows.nbytes
+            a = np.ascontiguousarray(a[rows.astype(np.int64)])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1238,7 +1270,8 @@ def main(argv=None):
     fs, dur, B_meas, desc = WORKLOADS[args.workload]
     est = make_estimator(args.workload)
     strong = args.workload in ("c4", "c5")
-    stage = "deconv" if strong else args.stage
+    # `--stage slice` outside a --pmc-child run has no timed leg of its own: K1 is what it times, for --steps steps
+    stage = "deconv" if strong or args.stage == "slice" else args.stage
     inv = np.asarray(est.inverse_filter, dtype=np.float64)
     M = len(est)
     if strong:
@@ -1304,6 +1337,10 @@ def main(argv=None):
     dec.set_timing(stride if stage == "deconv" else 0)
     dec_elapsed = timed_steps(dec, dec_steps, args.warmup if stage == "deconv" else 1)
     k1_ms, k1_n = dec.timing()
+    dumped = None
+    if stage == "deconv" and args.dump_outputs and rank == 0:
+        # the rows the last K1 launch group of the last timed step wrote (every block holds the same recordings)
+        dumped = dump_outputs(args.dump_outputs, [("deconv_outputs", dec.outputs()[(dec.n - 1) % len(dec.lanes)])])
     # the same kernels with nothing else on the chip (launch groups strictly serial: one stream), outside the timed
     # region: under overlap a kernel's event-to-event time includes the share of the chip it cedes to the other groups
     barrier(dec)
@@ -1363,6 +1400,10 @@ def main(argv=None):
         chain_k1, chain_k5 = team.timing()
         team.set_timing(0)
         y_chain, pk_chain = team.fetch(-1)
+        if args.dump_outputs and rank == 0:
+            # what a caller of the chain receives from the last call of the last timed step: equalised responses, peak indices
+            y_last, pk_last = team.fetch((team.next - 1) % len(team.lanes))
+            dumped = dump_outputs(args.dump_outputs, [("chain_outputs", y_last), ("chain_peak_indices", pk_last)])
         firs = team.firs
         peaks_ok &= all(abs(int(pk_chain[c]) - (M // 2 + delays[c])) <= 8 for c in range(B))   # exact check: against the oracle below
     if dist is not None:                      # rank 0 reports the verdict of every rank
@@ -1566,6 +1607,8 @@ def main(argv=None):
                                 other_plan=pair_block),
             "slice": whole_slice, "slice_resident": slice_res, "strong_c5": strong_c5,
         }
+        if dumped is not None:
+            sys.stderr.write(f"[bench] --dump-outputs {args.dump_outputs}: {json.dumps(dumped)}\n")
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(result) + "\n").encode())
     if dist is not None:
