@@ -1030,41 +1030,64 @@ __global__ __launch_bounds__(256, 4) void rows_single_kernel(RowsPairArgs args, 
 
 // ---------------------------------------------------------------------------------------------
 // K5 as ONE launch: overlap-save blocks that never leave the CU (core/impulse_response.py:110-119 equalize / :126-135
-// convolve, core/parallel_workers.py:9-21: x[n] (*) fir[K], K <= 24 577).  A workgroup of 1024 threads owns one
-// (channel, block): 32 768 input samples starting kp = K - 1 (rounded up to even) before the block's first output, as a
-// four-row four-step transform held in registers and LDS:
-//   load      four columns per thread (eight loads in flight at a time), radix-4 over the four rows, x the four-step twiddle,
-//             through LDS [4][4096] to the threads that own the rows (a thread reading all four rows of its 16 row-pass
-//             columns instead was 2.5x slower: sixteen dependent round trips to memory)
-//   rows      rows_core on the row pairs (0, 2) and (1, 3): forward FFT4096, W = alpha Z + beta conj Z[Nc - k] with the
-//             channel's own alpha/beta planes (those of a 4-row plan), inverse FFT4096
-//   store     rows -> LDS [4][4096] -> inverse radix-4 per column -> the 32 768 - kp valid samples of the block
+// convolve, core/parallel_workers.py:9-21: x[n] (*) fir[K], K <= 24 577).  A workgroup of 256 N1 threads owns one
+// (channel, block): 8192 N1 input samples starting kp = K - 1 (rounded up to even) before the block's first output, as an
+// N1-row four-step transform held in registers and LDS:
+//   load      N1 = 4: four columns per thread (eight loads in flight at a time), radix-4 over the four rows;
+//             N1 = 2: eight columns per thread (eight loads in flight at a time), radix-2 over the two rows;
+//             x the four-step twiddle, through LDS [N1][4096] to the threads that own the rows (a thread reading all rows
+//             of its 16 row-pass columns instead was 2.5x slower: sixteen dependent round trips to memory)
+//   rows      rows_core on the row pairs (0, 2) and (1, 3) (N1 = 2: the self-paired pair (0, 1)): forward FFT4096,
+//             W = alpha Z + beta conj Z[Nc - k] with the channel's own alpha/beta planes (those of an N1-row plan),
+//             inverse FFT4096
+//   store     rows -> LDS [N1][4096] -> inverse radix-N1 per column -> the 8192 N1 - kp valid samples of the block
 // Against the three-launch short plan (8 rows of workspace, three kernels of 128 - 512 small workgroups): no workspace
 // traffic at all, one launch, and the spectrum planes are half as long.
+// N1 = 4 (32 768 samples, 1024 threads, 136 KiB of LDS) is the plans' geometry.  N1 = 2 (16 384 samples, 512 threads,
+// 68 KiB) is the chain's for filters of up to 12 289 taps: its workgroup fits wherever a rows_kernel workgroup fits, so K5
+// shares CUs with the deconvolution passes of the other chains in flight instead of waiting for a CU to drain.
 // ---------------------------------------------------------------------------------------------
 struct FirBlockArgs {
-  const float4* __restrict__ ab;   // [n_filters][4][4096], register order of rows_core
-  long long ab_chan_stride;        // 0: one filter shared by all channels; 4 * 4096: per channel
+  const float4* __restrict__ ab;   // [n_filters][N1][4096], register order of rows_core
+  long long ab_chan_stride;        // 0: one filter shared by all channels; N1 * 4096: per channel
   float* __restrict__ out;
   long long out_stride;            // samples between output rows
   long long out_start, out_len;    // window of the linear convolution that is kept ('full': 0, L + M - 1)
   int kp;                          // taps - 1 rounded up to even: samples of history a block starts with
-  int valid;                       // 32768 - kp output samples per block
+  int valid;                       // 8192 N1 - kp output samples per block
   int blocks;                      // blocks per channel in this launch
   int first_block;                 // the launch's block 0 is block first_block of the convolution ('same': the window starts late)
   int nchan;
 };
 
-constexpr int kFirBlockPoints = 4 * kN2;                       // complex points of a block
-constexpr size_t kFirBlockLds = sizeof(cf) * 4 * 16 * kRowPad;
+template <int N1>
+struct FirBlockCfg {
+  static_assert(N1 == 2 || N1 == 4, "fir_block_kernel holds two or four rows");
+  static constexpr int kThreads = 256 * N1;
+  static constexpr int kPoints = N1 * kN2;                     // complex points of a block
+  static constexpr size_t kLds = sizeof(cf) * N1 * 16 * kRowPad;
+  // the 1024-thread workgroup leaves 128 VGPRs: four alpha/beta bins prefetched instead of the row pass's eight
+  static constexpr int kAbPrefetch = N1 == 4 ? 4 : ::imp::kAbPrefetch;
+};
+constexpr int kFirBlockPoints = FirBlockCfg<4>::kPoints;
+constexpr size_t kFirBlockLds = FirBlockCfg<4>::kLds;
 
 // a loader whose row lengths live in device memory (slice_kernels.hip.h LoadRowsDeviceLen): the kernel then takes the
 // kept window's length and the filter of a row from the loader, and the blocks past a row's end exit at once
 template <class L, class = void> struct LoadHasDeviceLen { static constexpr bool value = false; };
 template <class L> struct LoadHasDeviceLen<L, decltype((void)L::kDeviceLen)> { static constexpr bool value = true; };
 
-template <class Load>
-__global__ __launch_bounds__(1024, 4) void fir_block_kernel(Load ld, FirBlockArgs a, Twiddles tw) {
+// The four-step twiddle of the N1-row block: w_{4096 N1}^(k1 n2).  `tw.full` is always the 4-row table of the fused plan
+// (w_16384^(k1 n2) at k1 * 4096 + n2), so the 2-row block reads its w_8192^n2 = w_16384^(2 n2) from row 2.
+template <int N1>
+__device__ __forceinline__ cf fir_twiddle(__amdgpu_buffer_rsrc_t r_full, int k1, int n2) {
+  return bload_cf(r_full, (unsigned)((k1 * (4 / N1)) * kN2 + n2) * 8u, 0u);
+}
+
+template <int N1, class Load>
+__global__ __launch_bounds__(FirBlockCfg<N1>::kThreads, 4) void fir_block_kernel(Load ld, FirBlockArgs a, Twiddles tw) {
+  using Cfg = FirBlockCfg<N1>;
+  constexpr int T = Cfg::kThreads;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   cf* lds = reinterpret_cast<cf*>(smem_raw);
   // a channel's blocks share its alpha/beta planes: keep them on one XCD (blocks b and b + 8 share an XCD)
@@ -1079,37 +1102,41 @@ __global__ __launch_bounds__(1024, 4) void fir_block_kernel(Load ld, FirBlockArg
     if ((long long)blk * a.valid - a.out_start >= out_len) return;   // the grid covers the longest row the plan allows
   }
   const int tid = threadIdx.x;
-  const int pairq = __builtin_amdgcn_readfirstlane(tid >> 9);  // 0: rows (0, 2), 1: rows (1, 3)
+  // N1 = 4: pairq 0 = rows (0, 2), 1 = rows (1, 3); N1 = 2: the one pair (0, 1).  half = which row of the pair.
+  const int pairq = N1 == 4 ? __builtin_amdgcn_readfirstlane(tid >> 9) : 0;
   const int half = __builtin_amdgcn_readfirstlane((tid >> 8) & 1);
   const int t = tid & 255;
-  const int k1 = pairq + 2 * half;
+  const int k1 = pairq + (N1 / 2) * half;
   const int s0 = blk * a.valid - a.kp;                         // even: first input sample of the block (|s0| < 2^29)
   const __amdgpu_buffer_rsrc_t r_full = make_rsrc(tw.full, 4u * kN2 * 8u);
   const auto row = ld.open(chan);
 
-  // columns n2 = tid + 1024 c: sixteen 8-byte loads and twelve twiddles in flight per thread, radix-4 over the rows,
-  // x the four-step twiddle, then through LDS [4][4096] to the threads that own the rows
+  // columns n2 = tid + T c, radix-N1 over the rows, x the four-step twiddle, then through LDS [N1][4096] to the threads
+  // that own the rows: two (N1 = 4) or four (N1 = 2) columns at a time, eight loads in flight
+  constexpr int CPT = kN2 / T;                                 // columns per thread
+  constexpr int CH = 8 / N1;                                   // columns per batch
   cf v[16];
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {                                // two columns at a time: eight loads + six twiddles in flight
-    cf x[2][4], w[2][3];
+  for (int h = 0; h < CPT / CH; ++h) {
+    cf x[CH][N1], w[CH][N1 - 1];
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int n2 = tid + 1024 * (2 * h + c);
+    for (int c = 0; c < CH; ++c) {
+      const int n2 = tid + T * (CH * h + c);
 #pragma unroll
-      for (int n1 = 0; n1 < 4; ++n1) x[c][n1] = row.pair_at(s0 + 2 * (n1 * kN2 + n2));
+      for (int n1 = 0; n1 < N1; ++n1) x[c][n1] = row.pair_at(s0 + 2 * (n1 * kN2 + n2));
 #pragma unroll
-      for (int k = 1; k < 4; ++k) w[c][k - 1] = bload_cf(r_full, (unsigned)(k * kN2 + n2) * 8u, 0u);
+      for (int k = 1; k < N1; ++k) w[c][k - 1] = fir_twiddle<N1>(r_full, k, n2);
     }
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int n2 = tid + 1024 * (2 * h + c);
+    for (int c = 0; c < CH; ++c) {
+      const int n2 = tid + T * (CH * h + c);
 #pragma unroll
-      for (int n1 = 0; n1 < 4; ++n1) x[c][n1] = row.finish(x[c][n1], s0 + 2 * (n1 * kN2 + n2));   // (the chain's fades)
-      bfly4<-1>(x[c][0], x[c][1], x[c][2], x[c][3]);
+      for (int n1 = 0; n1 < N1; ++n1) x[c][n1] = row.finish(x[c][n1], s0 + 2 * (n1 * kN2 + n2));   // (the chain's fades)
+      if constexpr (N1 == 4) bfly4<-1>(x[c][0], x[c][1], x[c][2], x[c][3]);
+      else bfly2<-1>(x[c][0], x[c][1]);
       lds[n2] = x[c][0];
 #pragma unroll
-      for (int k = 1; k < 4; ++k) lds[k * kN2 + n2] = cmul(x[c][k], w[c][k - 1]);
+      for (int k = 1; k < N1; ++k) lds[k * kN2 + n2] = cmul(x[c][k], w[c][k - 1]);
     }
   }
   __syncthreads();
@@ -1118,8 +1145,7 @@ __global__ __launch_bounds__(1024, 4) void fir_block_kernel(Load ld, FirBlockArg
   __syncthreads();                                             // rows_core reuses the same LDS
   const __amdgpu_buffer_rsrc_t r_ab =
       make_rsrc(a.ab + (long long)filt * a.ab_chan_stride + (long long)k1 * kN2, kN2 * sizeof(float4));
-  // (16 waves per CU leave 128 VGPRs: four alpha/beta bins prefetched instead of the row pass's eight)
-  rows_core<0, 4>(v, lds + pairq * (2 * 16 * kRowPad), half, pairq, k1, r_ab, tw, t);
+  rows_core<0, Cfg::kAbPrefetch>(v, lds + pairq * (2 * 16 * kRowPad), half, pairq, k1, r_ab, tw, t);
 
   __syncthreads();                                             // every plane is free
 #pragma unroll
@@ -1128,16 +1154,17 @@ __global__ __launch_bounds__(1024, 4) void fir_block_kernel(Load ld, FirBlockArg
   const __amdgpu_buffer_rsrc_t r_out = make_rsrc(a.out + (long long)chan * a.out_stride, (unsigned)out_len * 4u);
   const int o0 = blk * a.valid - a.kp - (int)a.out_start;      // output index of the block's position 0
 #pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int n2 = tid + 1024 * c;
-    cf w0 = lds[n2], w1 = lds[kN2 + n2], w2 = lds[2 * kN2 + n2], w3 = lds[3 * kN2 + n2];
-    w1 = cmulc(w1, bload_cf(r_full, (unsigned)(kN2 + n2) * 8u, 0u));
-    w2 = cmulc(w2, bload_cf(r_full, (unsigned)(2 * kN2 + n2) * 8u, 0u));
-    w3 = cmulc(w3, bload_cf(r_full, (unsigned)(3 * kN2 + n2) * 8u, 0u));
-    bfly4<+1>(w0, w1, w2, w3);                                 // samples 2 (n1 4096 + n2), + 1 of the block, n1 = 0..3
-    const cf y[4] = {w0, w1, w2, w3};
+  for (int c = 0; c < CPT; ++c) {
+    const int n2 = tid + T * c;
+    cf y[N1];
 #pragma unroll
-    for (int n1 = 0; n1 < 4; ++n1) {
+    for (int k = 0; k < N1; ++k) y[k] = lds[k * kN2 + n2];
+#pragma unroll
+    for (int k = 1; k < N1; ++k) y[k] = cmulc(y[k], fir_twiddle<N1>(r_full, k, n2));
+    if constexpr (N1 == 4) bfly4<+1>(y[0], y[1], y[2], y[3]);  // samples 2 (n1 4096 + n2), + 1 of the block, n1 = 0..N1-1
+    else bfly2<+1>(y[0], y[1]);
+#pragma unroll
+    for (int n1 = 0; n1 < N1; ++n1) {
       const int pos = 2 * (n1 * kN2 + n2);
       if (pos < a.kp) continue;                                // the block's history: wrapped-around garbage
       // the window's two edges fall to the range check (an offset below the window wraps out of range); an odd window

@@ -510,6 +510,10 @@ struct imp_plan {
   bool fused = false;
   int f_kp = 0, f_valid = 0;        // history samples a block starts with (taps - 1, even), outputs per block
   int64_t f_first = 0, f_blocks = 0; // first block that touches the kept window, blocks per channel
+  // spectrum generation: bumped whenever the planes may have changed.  Fused plans whose filters fit the chain's 2-row K5
+  // (imp_chain) also keep the taps on the device, fp64 [n_filters][M], valid while taps_gen == filter_gen.
+  int64_t filter_gen = 0, taps_gen = -1;
+  double* d_taps = nullptr;
   // pair mode (conv_kernels.hip.h): two channels per transform, z = x_L + i x_R; Nc = nfft = circular length in samples
   bool paired = false;
   cf* hs = nullptr;        // [N1][4096]: H / Nc in the register order of rows_single_kernel
@@ -653,6 +657,8 @@ static int launch_rows_single(imp_plan* p, int64_t npairs) {
 
 // taps a fused FIR plan takes: a block then still yields 8 191 or more of its 32 768 samples
 static constexpr int64_t kFusedMaxTaps = 24577;
+// taps the chain's 2-row K5 takes (fir_block_kernel<2>): a block of 16 384 samples then still yields 4 096 or more
+static constexpr int64_t kChainTail2MaxTaps = 16384 - 4096 + 1;
 
 static int plan_geometry(imp_plan* p, int64_t M, int64_t n_filters, int64_t L, int mode, int64_t ws_channels,
                          bool paired = false, bool allow_fused = true) {
@@ -787,6 +793,7 @@ extern "C" void imp_plan_destroy(imp_plan* p) {
   (void)plan_sync_lanes(p);
   if (p->ab) (void)hipFree(p->ab);
   if (p->hs) (void)hipFree(p->hs);
+  if (p->d_taps) (void)hipFree(p->d_taps);
   if (p->ws) (void)hipFree(p->ws);
   if (p->d_in) (void)hipFree(p->d_in);
   if (p->d_out) (void)hipFree(p->d_out);
@@ -824,7 +831,7 @@ extern "C" int imp_conv_plan_create_empty_paired(imp_ctx* ctx, int64_t M, int64_
 
 // the plan's spectrum planes from host filters (fp64 on the device, rounded once); work in flight must be drained.
 // on_device: the filters are device memory (mono / fused plans without overlap-add): nothing is uploaded and nothing waits.
-static int plan_fill_spectrum(imp_plan* p, const double* filter, int64_t filter_ld, bool on_device = false) {
+static int plan_fill_planes(imp_plan* p, const double* filter, int64_t filter_ld, bool on_device) {
   imp_ctx* ctx = p->ctx;
   const int64_t M = p->M, n_filters = p->n_filters;
   const int64_t ld = n_filters > 1 ? filter_ld : M;
@@ -859,6 +866,25 @@ static int plan_fill_spectrum(imp_plan* p, const double* filter, int64_t filter_
       if (rc) return rc;
     }
   }
+  return IMP_OK;
+}
+
+static int plan_fill_spectrum(imp_plan* p, const double* filter, int64_t filter_ld, bool on_device = false) {
+  ++p->filter_gen;
+  int rc = plan_fill_planes(p, filter, filter_ld, on_device);
+  if (rc || !p->fused || p->M > kChainTail2MaxTaps) return rc;
+  // the taps themselves, for the chain's 2-row spectrum planes (imp_chain prepares them from here)
+  const int64_t ld = p->n_filters > 1 ? filter_ld : p->M;
+  const size_t row = (size_t)p->M * sizeof(double);
+  if (!p->d_taps && hipMalloc((void**)&p->d_taps, row * (size_t)p->n_filters) != hipSuccess) {
+    (void)hipGetLastError();
+    p->d_taps = nullptr;
+    return IMP_OK;                                  // no copy: chains take the 4-row K5
+  }
+  HIP_TRY(hipMemcpy2DAsync(p->d_taps, row, filter, (size_t)ld * sizeof(double), row, (size_t)p->n_filters,
+                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, p->ctx->stream));
+  if (!on_device) HIP_TRY(hipStreamSynchronize(p->ctx->stream));   // the caller may reuse the host rows after return
+  p->taps_gen = p->filter_gen;
   return IMP_OK;
 }
 
@@ -993,6 +1019,7 @@ extern "C" int imp_plan_info(const imp_plan* p, int64_t* nfft, int64_t* out_len,
 extern "C" int imp_plan_spectrum(imp_plan* p, void** dptr, size_t* bytes) {
   if (!p || !dptr || !bytes) return fail(IMP_ERR_INVALID, "imp_plan_spectrum: null argument");
   IMP_CTX_LOCK(p->ctx);
+  ++p->filter_gen;                                   // the planes may be written through the pointer: the taps no longer match
   if (p->paired) {
     *dptr = p->hs;
     *bytes = (size_t)p->N1 * imp::kN2 * sizeof(cf);
@@ -1015,7 +1042,9 @@ extern "C" int imp_plan_copy_spectrum(imp_plan* dst, imp_plan* src) {
   void *d = nullptr, *s_ = nullptr;
   size_t nd = 0, ns = 0;
   int rc;
+  const int64_t src_gen = src->filter_gen;
   if ((rc = imp_plan_spectrum(src, &s_, &ns)) || (rc = imp_plan_spectrum(dst, &d, &nd))) return rc;
+  src->filter_gen = src_gen;                             // src is only read (dst keeps its bump: its taps are stale)
   if (nd != ns) return fail(IMP_ERR_INVALID, "imp_plan_copy_spectrum: spectrum sizes differ");
   {
     IMP_CTX_LOCK(src->ctx);                              // the source must be complete
@@ -1119,29 +1148,39 @@ template <class Load>
 static int run_group_with(imp_plan* p, Load ld, int64_t nchan, float* d_y, int64_t chan_stride_out,
                           int64_t first_chan, int last_stage);
 
-template <class Load>
-static int launch_fir_block(imp_plan* p, Load ld, int64_t nchan, float* d_y, int64_t chan_stride_out, int64_t first_chan) {
-  auto kern = imp::fir_block_kernel<Load>;
-  int rc = ctx_kernel_lds(p->ctx, reinterpret_cast<const void*>(kern), imp::kFirBlockLds);
+// fir_block_kernel<N1> over `nchan` channels: ab = the planes of the group's first channel (N1 rows each), blocks of kp
+// history samples and `valid` outputs, blocks [first, first + blocks) of every channel
+template <int N1, class Load>
+static int launch_fir_block_rows(imp_plan* p, Load ld, int64_t nchan, float* d_y, int64_t chan_stride_out, const float4* ab,
+                                 int kp, int valid, int64_t first, int64_t blocks) {
+  using Cfg = imp::FirBlockCfg<N1>;
+  auto kern = imp::fir_block_kernel<N1, Load>;
+  int rc = ctx_kernel_lds(p->ctx, reinterpret_cast<const void*>(kern), Cfg::kLds);
   if (rc) return rc;
-  const int64_t plane = (int64_t)4 * imp::kN2;
   imp::FirBlockArgs a;
-  a.ab = p->ab + (p->n_filters > 1 ? first_chan * plane : 0);
-  a.ab_chan_stride = p->n_filters > 1 ? plane : 0;
+  a.ab = ab;
+  a.ab_chan_stride = p->n_filters > 1 ? (int64_t)N1 * imp::kN2 : 0;
   a.out = d_y;
   a.out_stride = chan_stride_out;
   a.out_start = p->out_start;
-  a.first_block = (int)p->f_first;
+  a.first_block = (int)first;
   a.out_len = p->out_len;
-  a.kp = p->f_kp;
-  a.valid = p->f_valid;
-  a.blocks = (int)p->f_blocks;
+  a.kp = kp;
+  a.valid = valid;
+  a.blocks = (int)blocks;
   a.nchan = (int)nchan;
   imp::Twiddles tw{p->tw.full, p->tw.hi, p->ctx->tw_t1, p->ctx->tw_t2, p->ctx->tw_t4};
-  dim3 grid((unsigned)((nchan + 7) / 8 * 8 * p->f_blocks)), block(1024);
-  hipLaunchKernelGGL(kern, grid, block, imp::kFirBlockLds, p->cur_stream, ld, a, tw);
+  dim3 grid((unsigned)((nchan + 7) / 8 * 8 * blocks)), block(Cfg::kThreads);
+  hipLaunchKernelGGL(kern, grid, block, Cfg::kLds, p->cur_stream, ld, a, tw);
   HIP_TRY(hipGetLastError());
   return IMP_OK;
+}
+
+// the plan's own geometry: 4 rows, its planes
+template <class Load>
+static int launch_fir_block(imp_plan* p, Load ld, int64_t nchan, float* d_y, int64_t chan_stride_out, int64_t first_chan) {
+  const float4* ab = p->ab + (p->n_filters > 1 ? first_chan * (int64_t)imp::kFirBlockPoints : 0);
+  return launch_fir_block_rows<4>(p, ld, nchan, d_y, chan_stride_out, ab, p->f_kp, p->f_valid, p->f_first, p->f_blocks);
 }
 
 // one launch group in pair mode: channels (2q, 2q + 1) of the group share a transform; ld.nchan = nchan
@@ -1580,7 +1619,43 @@ struct imp_chain {
   std::vector<char> ir_busy;
   int64_t* d_meta = nullptr;        // off[B], len[B]
   double* d_win = nullptr;          // the two Hann fades as tables (LoadCropAtPeak)
+  // K5 as 2-row blocks (fir_block_kernel<2>, 512 threads, 68 KiB of LDS) when the FIR plan's filters fit: the chain's own
+  // alpha/beta planes [n_filters][2][4096], made from the plan's taps, current while ab2_gen == fir->filter_gen
+  float4* d_ab2 = nullptr;
+  int64_t ab2_gen = -1;
+  int t2_kp = 0, t2_valid = 0;
+  int64_t t2_first = 0, t2_blocks = 0;
 };
+
+// Geometry of the chain's 2-row K5: blocks of 16 384 samples that start kp = taps - 1 (rounded up to even) samples early;
+// false when a block would yield fewer than 4 096 outputs (the 4-row K5 takes those filters)
+static bool chain_tail2_geometry(int64_t M, int64_t out_start, int64_t out_len, int* kp, int* valid, int64_t* first,
+                                 int64_t* blocks) {
+  if (M < 1 || M > kChainTail2MaxTaps) return false;
+  *kp = (int)((M - 1 + 1) & ~(int64_t)1);
+  *valid = (int)(2 * imp::FirBlockCfg<2>::kPoints - *kp);
+  *first = out_start / *valid;
+  *blocks = (out_start + out_len - 1) / *valid - *first + 1;
+  return true;
+}
+
+// (re)makes the 2-row planes from the FIR plan's taps on its stream, behind every K5 queued before; false when the plan
+// holds no current taps (its spectrum arrived by copy or broadcast): that call takes the 4-row K5
+static int chain_tail2_prepare(imp_chain* c, bool* ready) {
+  imp_plan* f = c->fir;
+  *ready = false;
+  if (!c->d_ab2) return IMP_OK;
+  if (c->ab2_gen == f->filter_gen) {
+    *ready = true;
+    return IMP_OK;
+  }
+  if (!f->d_taps || f->taps_gen != f->filter_gen) return IMP_OK;
+  int rc = spectrum_alpha_beta_device(f->ctx, f->d_taps, f->M, f->n_filters, f->M, imp::FirBlockCfg<2>::kPoints, 2, c->d_ab2, true);
+  if (rc) return rc;
+  c->ab2_gen = f->filter_gen;
+  *ready = true;
+  return IMP_OK;
+}
 
 // both contexts, in address order
 struct ChainLock {
@@ -1610,6 +1685,7 @@ extern "C" void imp_chain_destroy(imp_chain* c) {
   for (auto e : c->ir_free) (void)hipEventDestroy(e);
   (void)hipFree(c->d_meta);
   (void)hipFree(c->d_win);
+  (void)hipFree(c->d_ab2);
   delete c;
 }
 
@@ -1688,6 +1764,18 @@ extern "C" int imp_chain_create(imp_plan* deconv, imp_plan* fir, int64_t B, int6
     if (e2) c->ir_free.push_back(e2);
   }
   c->ir_busy.assign((size_t)c->sets, 0);
+  // IMPULSE_HIP_CHAIN_K5=block4 keeps the plan's 4-row K5 (A/B runs)
+  const char* k5_env = std::getenv("IMPULSE_HIP_CHAIN_K5");
+  const bool block4 = k5_env && std::strcmp(k5_env, "block4") == 0;
+  if (ok && fir->fused && !block4 &&
+      chain_tail2_geometry(fir->M, fir->out_start, fir->out_len, &c->t2_kp, &c->t2_valid, &c->t2_first, &c->t2_blocks)) {
+    ok = hipMalloc((void**)&c->d_ab2, (size_t)fir->n_filters * imp::FirBlockCfg<2>::kPoints * sizeof(float4)) == hipSuccess;
+    bool ready = false;
+    if (ok && (rc = chain_tail2_prepare(c, &ready))) {
+      imp_chain_destroy(c);
+      return rc;
+    }
+  }
   if (!ok) {
     (void)hipGetLastError();
     imp_chain_destroy(c);
@@ -1731,11 +1819,47 @@ extern "C" int imp_chain_execute_device(imp_chain* c, const float* d_x, int64_t 
   HIP_TRY(hipGetLastError());
   imp::LoadCropAtPeak ld{c->d_ir[(size_t)l], c->pitch_ir, c->deconv->out_len, c->d_res[(size_t)l], c->n, c->head, c->fade_in, c->fade_out,
                          c->d_win};
-  if ((rc = run_group_with(c->fir, ld, c->B, d_out, chan_stride_out, 0, 2))) return rc;
+  bool tail2 = false;
+  if ((rc = chain_tail2_prepare(c, &tail2))) return rc;
+  if (tail2) {
+    // the FIR plan's stream (lanes = 1) and its timing slots, as run_group_with brackets a fused launch
+    imp_plan* f = c->fir;
+    f->cur_stream = f->ctx->stream;
+    if ((rc = timing_event(f, 0))) return rc;
+    if ((rc = launch_fir_block_rows<2>(f, ld, c->B, d_out, chan_stride_out, c->d_ab2, c->t2_kp, c->t2_valid, c->t2_first,
+                                       c->t2_blocks)))
+      return rc;
+    for (int slot = 1; slot <= 3; ++slot)
+      if ((rc = timing_event(f, slot))) return rc;
+  } else if ((rc = run_group_with(c->fir, ld, c->B, d_out, chan_stride_out, 0, 2))) {
+    return rc;
+  }
   if (tail != lane_stream) {
     HIP_TRY(hipEventRecord(c->ir_free[(size_t)l], tail));
     c->ir_busy[(size_t)l] = 1;
   }
+  return IMP_OK;
+}
+
+// rows of the K5 blocks the chain's next call runs: 2 (fir_block_kernel<2>) or 4 (the FIR plan's own launch)
+extern "C" int imp_chain_tail_rows(imp_chain* c, int* rows) {
+  if (!c || !rows) return fail(IMP_ERR_INVALID, "imp_chain_tail_rows: null argument");
+  ChainLock lk(c->ctx, c->tail_ctx);
+  imp_plan* f = c->fir;
+  *rows = c->d_ab2 && (c->ab2_gen == f->filter_gen || (f->d_taps && f->taps_gen == f->filter_gen)) ? 2 : 4;
+  return IMP_OK;
+}
+
+extern "C" int imp_debug_chain_tail_geometry(int64_t M, int64_t L, int64_t* history, int64_t* valid, int64_t* blocks) {
+  if (L < 1) return fail(IMP_ERR_INVALID, "L must be >= 1 (got %lld)", (long long)L);
+  int kp = 0, v = 0;
+  int64_t first = 0, nb = 0;
+  if (!chain_tail2_geometry(M, 0, L + M - 1, &kp, &v, &first, &nb))
+    return fail(IMP_ERR_UNSUPPORTED, "the chain's 2-row K5 takes 1 to %lld taps (got %lld)", (long long)kChainTail2MaxTaps,
+                (long long)M);
+  if (history) *history = kp;
+  if (valid) *valid = v;
+  if (blocks) *blocks = nb;
   return IMP_OK;
 }
 

@@ -120,6 +120,7 @@ SIGNATURES = {
     "imp_chain_create": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, C.c_double, C.POINTER(_vp)]),
     "imp_chain_execute_device": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp]),
     "imp_chain_destroy": (None, [_vp]),
+    "imp_chain_tail_rows": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "imp_slice_create": (C.c_int, [_vp, C.POINTER(SliceGeometry), _i64, C.POINTER(_vp)]),
     "imp_slice_destroy": (None, [_vp]),
     "imp_slice_info": (C.c_int, [_vp, _pi64, _pi64, _pi64, _pi64]),
@@ -149,6 +150,7 @@ SIGNATURES = {
     "imp_plan_get_timing": (C.c_int, [_vp, _pd, _pi64, C.c_int]),
     "imp_debug_plan_geometry": (C.c_int, [_i64, _i64, C.c_int, _pi64, _pi64, _pi64]),
     "imp_debug_plan_geometry_fused": (C.c_int, [_i64, _i64, C.c_int, _pi64, _pi64, _pi64, _pi64]),
+    "imp_debug_chain_tail_geometry": (C.c_int, [_i64, _i64, _pi64, _pi64, _pi64]),
     "imp_debug_plan_geometry_paired": (C.c_int, [_i64, _i64, C.c_int, _pi64, _pi64, _pi64, _pi64]),
     "imp_debug_host_spectrum": (C.c_int, [_pd, _i64, C.c_int, _pf]),
     "imp_plan_debug_run_stage": (C.c_int, [_vp, _pf, _i64, _i64, C.c_int, _pf]),
@@ -672,6 +674,12 @@ class FirChain:
             raise NativeError(-1, "the chain is closed (one of its contexts was closed)")
         _check(self._lib.imp_chain_execute_device(self._h, _vp(int(d_x)), int(chan_stride_in), int(elem_stride_in),
                                                   _vp(int(d_out)), int(chan_stride_out), _vp(int(d_peaks)) if d_peaks else None))
+
+    def tail_rows(self):
+        """Rows of the K5 blocks the next call runs: 2 (16 384-sample blocks) or 4 (the FIR plan's 32 768)."""
+        r = C.c_int()
+        _check(self._lib.imp_chain_tail_rows(self._h, C.byref(r)))
+        return r.value
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1317,6 +1325,18 @@ def plan_geometry_fused(M, L, mode="same"):
         return None
     _check(rc)
     return a.value, b.value, c.value, d.value
+
+
+def chain_tail_geometry(M, L):
+    """(history, valid, blocks) of a chain's 2-row K5 for a 'full' FIR of M taps over L samples, or None beyond 12 289
+    taps (the chain then runs the FIR plan's 4-row blocks); needs no GPU."""
+    lib = load_library()
+    a, b, c = _i64(), _i64(), _i64()
+    rc = lib.imp_debug_chain_tail_geometry(int(M), int(L), C.byref(a), C.byref(b), C.byref(c))
+    if rc == IMP_ERR_UNSUPPORTED:
+        return None
+    _check(rc)
+    return a.value, b.value, c.value
 
 
 def plan_geometry_paired(M, L, mode="same"):

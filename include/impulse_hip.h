@@ -438,6 +438,14 @@ int imp_chain_create(imp_plan* deconv, imp_plan* fir, int64_t B, int64_t head, i
 int imp_chain_execute_device(imp_chain* chain, const float* d_x, int64_t chan_stride_in, int64_t elem_stride_in,
                              float* d_out, int64_t chan_stride_out, long long* d_peaks_out);
 void imp_chain_destroy(imp_chain* chain);
+/* K5 of a chain whose FIR plan is fused and has at most 12 289 taps runs as blocks of 16 384 samples (two four-step rows,
+ * 512 threads; the chain prepares its own spectrum planes from the plan's taps, again after every refill), otherwise as
+ * the plan's blocks of 32 768 (four rows); IMPULSE_HIP_CHAIN_K5=block4 at creation keeps the latter.
+ * imp_chain_tail_rows: the rows of the blocks the next call runs (2 or 4).  imp_debug_chain_tail_geometry: history,
+ * outputs per block and blocks per channel of the 2-row blocks for a 'full' FIR of M taps over L samples;
+ * IMP_ERR_UNSUPPORTED beyond 12 289 taps.  Needs no GPU. */
+int imp_chain_tail_rows(imp_chain* chain, int* rows);
+int imp_debug_chain_tail_geometry(int64_t M, int64_t L, int64_t* history, int64_t* valid, int64_t* blocks);
 
 /* ---- the reference's stage sequence, device resident and batched ----------------------------------------------------
  * core/pipeline.py:565-573 (open measurements) -> :585-601 (crop_heads, crop_tails) -> :647-692 (equalize) -> :725-735
