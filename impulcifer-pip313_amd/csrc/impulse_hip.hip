@@ -22,6 +22,7 @@
 #include "ir_kernels.hip.h"
 #include "decay_kernels.hip.h"      // it switches fp contraction off for what follows
 #include "slice_kernels.hip.h"
+#include "vbass_kernels.hip.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -2257,6 +2258,100 @@ extern "C" int imp_sosfilt(imp_ctx* ctx, const double* sos, int64_t n_sections, 
     std::swap(d_x, d_y);
   }
   std::swap(d_x, d_y);                                     // d_y = output of the last chunk
+  HIP_TRY(hipMemcpyAsync(y, d_y, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return IMP_OK;
+}
+
+// The chunk-parallel cascade (vbass_kernels.hip.h): sections as kernel arguments, identity past n_sections; 0 or an error
+static int iir_sos_from(const double* sos, int64_t n_sections, imp::IirSos* f, const char* who) {
+  if (n_sections < 1 || n_sections > imp::kMaxSections)
+    return fail(IMP_ERR_UNSUPPORTED, "%s: cascades of 1 .. %d sections; got %lld", who, imp::kMaxSections, (long long)n_sections);
+  for (int s = 0; s < imp::kMaxSections; ++s) {
+    const bool on = s < n_sections;
+    if (on) {
+      if (sos[6 * s + 3] != 1.0) return fail(IMP_ERR_INVALID, "%s: section %d is not normalised (a0 != 1)", who, s);
+      for (int j = 0; j < 6; ++j)
+        if (!std::isfinite(sos[6 * s + j])) return fail(IMP_ERR_INVALID, "%s: section %d has a non-finite coefficient", who, s);
+    }
+    f->b0[s] = on ? sos[6 * s + 0] : 1.0;
+    f->b1[s] = on ? sos[6 * s + 1] : 0.0;
+    f->b2[s] = on ? sos[6 * s + 2] : 0.0;
+    f->a1[s] = on ? sos[6 * s + 4] : 0.0;
+    f->a2[s] = on ? sos[6 * s + 5] : 0.0;
+  }
+  f->n = (int)n_sections;
+  return IMP_OK;
+}
+
+// P = A^steps of the cascade's state (z0, z1 of section s at 2 s, 2 s + 1): column j is the state after `steps` samples of zero
+// input from unit state j, run in extended precision
+static void iir_transition(const imp::IirSos& f, int steps, double* P) {
+  constexpr int S = imp::kMaxSections;
+  for (int j = 0; j < 2 * S; ++j) {
+    long double z0[S] = {}, z1[S] = {};
+    (j & 1 ? z1 : z0)[j >> 1] = 1.0L;
+    for (int i = 0; i < steps; ++i) {
+      long double cur = 0.0L;
+      for (int s = 0; s < S; ++s) {
+        const long double out = (long double)f.b0[s] * cur + z0[s];
+        z0[s] = (long double)f.b1[s] * cur - (long double)f.a1[s] * out + z1[s];
+        z1[s] = (long double)f.b2[s] * cur - (long double)f.a2[s] * out;
+        cur = out;
+      }
+    }
+    for (int s = 0; s < S; ++s) {
+      P[(2 * s) * 2 * S + j] = (double)z0[s];
+      P[(2 * s + 1) * 2 * S + j] = (double)z1[s];
+    }
+  }
+}
+
+extern "C" int imp_sosfilt_chunked(imp_ctx* ctx, const double* sos, int64_t n_sections, const double* x, const int64_t* off,
+                                   const int64_t* len, int64_t B, double* y) {
+  if (!ctx || !sos || (B && (!x || !off || !len || !y))) return fail(IMP_ERR_INVALID, "imp_sosfilt_chunked: null argument");
+  IMP_CTX_LOCK(ctx);
+  imp::IirSos f;
+  int rc = iir_sos_from(sos, n_sections, &f, "imp_sosfilt_chunked");
+  if (rc) return rc;
+  if (B < 0 || B > 65535) return fail(IMP_ERR_INVALID, "imp_sosfilt_chunked: B must be in [0, 65535]");
+  if (B == 0) return IMP_OK;
+  int64_t total = 0, longest = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in row %lld", (long long)b);
+    total = std::max(total, off[b] + len[b]);
+    longest = std::max(longest, len[b]);
+  }
+  if (total == 0 || longest == 0) return IMP_OK;
+  if ((rc = ctx_bind(ctx))) return rc;
+  hipStream_t st = ctx->stream;
+  const int64_t cp = (longest + imp::kIirChunk - 1) / imp::kIirChunk;
+  const size_t states = (size_t)(B * cp) * imp::kIirState;
+  const size_t bytes = ((size_t)(2 * total + 256) + 2 * states) * sizeof(double) + (size_t)(2 * B) * sizeof(int64_t);
+  void* buf = nullptr;
+  if ((rc = ctx_scratch(ctx, bytes, &buf))) return rc;
+  double* d_x = (double*)buf;
+  double* d_y = d_x + total;
+  double* d_P = d_y + total;
+  double* d_end = d_P + 256;
+  double* d_init = d_end + states;
+  int64_t* d_off = (int64_t*)(d_init + states);
+  int64_t* d_len = d_off + B;
+  std::vector<double> P(256);
+  iir_transition(f, imp::kIirChunk, P.data());
+  HIP_TRY(hipMemcpyAsync(d_x, x, (size_t)total * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(d_y, 0, (size_t)total * sizeof(double), st));
+  HIP_TRY(hipMemcpyAsync(d_P, P.data(), 256 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_off, off, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_len, len, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  const dim3 grid((unsigned)((cp + 63) / 64), (unsigned)B);
+  hipLaunchKernelGGL(imp::iir_chunk_end_kernel<double>, grid, dim3(64), 0, st, f, (const double*)d_x, (const int64_t*)d_off,
+                     (const int64_t*)d_len, d_end, (long long)cp);
+  hipLaunchKernelGGL(imp::iir_carry_kernel, dim3((unsigned)B), dim3(64), 0, st, (const double*)d_P, (const int64_t*)d_len,
+                     (const double*)d_end, d_init, (long long)cp);
+  hipLaunchKernelGGL(imp::iir_chunk_out_kernel<double>, grid, dim3(64), 0, st, f, (const double*)d_x, (const int64_t*)d_off,
+                     (const int64_t*)d_len, (const double*)d_init, (long long)cp, d_y);
+  HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(y, d_y, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return IMP_OK;

@@ -58,6 +58,24 @@ struct imp_slice {
   int64_t* d_off_al = nullptr;       // [B] where the later stages read row b: crop_heads' place or its materialised copy
   double *d_xval = nullptr, *d_xpart_val = nullptr;
   imp::RowPeak* d_res1 = nullptr;
+  // virtual bass between crop_tails and equalize (imp_slice_set_virtual_bass)
+  bool vb_on = false;
+  imp::IirSos vb_sos{};
+  double vb_xo = 0, vb_pol = 1;
+  int64_t vb_head = 0, vb_chunks = 0, vb_spans = 0, vb_hi_pitch = 0;
+  char* d_vbblock = nullptr;         // one allocation: the tables below
+  float* d_vb = nullptr;             // [B][pitch_crop] the cropped rows, then hi + synth: what K5 reads
+  double *d_vb_end = nullptr, *d_vb_init = nullptr;   // [B][vb_chunks][16] chunk states of the IIR scan
+  double *d_vb_part = nullptr, *d_vb_refp = nullptr;  // DFT partial sums: [B][vb_chunks][2], [m_cap][vb_spans][2]
+  double *d_vb_mp = nullptr, *d_vb_ild = nullptr;     // [keep_cap] mpbass, ild_mpbass
+  double *d_vb_P = nullptr, *d_vb_gp = nullptr;       // A^L [16][16]; g * polarity per measurement
+  int* d_vb_left = nullptr;          // [n_pairs]
+  int64_t *d_vb_off = nullptr, *d_vb_len = nullptr;
+  imp::WindowParams* d_vb_par = nullptr;
+  long long* d_vb_bin = nullptr;
+  imp::VbRow* d_vb_rows = nullptr;
+  imp::RowPeak* d_vb_res = nullptr;
+  double* d_vb_hi = nullptr;         // the caller's: fp64 high-passed rows of the next calls (imp_slice_vbass_hi_device)
   // pinned host copies of the results of the last call
   imp::SliceRowOut* h_rows = nullptr;
   imp::SliceMeasOut* h_meas = nullptr;
@@ -87,6 +105,7 @@ extern "C" void imp_slice_destroy(imp_slice* s) {
   (void)hipFree(s->d_dscr);
   (void)hipFree(s->d_ir2);
   (void)hipFree(s->d_ablock);
+  (void)hipFree(s->d_vbblock);
   if (s->h_rows) (void)hipHostFree(s->h_rows);
   if (s->h_meas) (void)hipHostFree(s->h_meas);
   delete s;
@@ -401,6 +420,139 @@ extern "C" int imp_slice_set_decay(imp_slice* s, const double* target_rt60) {
   return IMP_OK;
 }
 
+extern "C" int imp_slice_set_virtual_bass(imp_slice* s, const double* sos_hp, int64_t n_sections, const double* mpbass,
+                                          const double* ild_mpbass, int64_t len, double crossover_freq, int64_t head,
+                                          int32_t invert_polarity, const int32_t* pair_on_left) {
+  if (!s) return fail(IMP_ERR_INVALID, "imp_slice_set_virtual_bass: null slice");
+  imp_ctx* ctx = s->ctx;
+  IMP_CTX_LOCK(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  const int64_t B = s->m_cap * s->R;
+  // off: no sections, or a crossover at or above Nyquist (core/virtual_bass.py:93-95 returns without touching the rows)
+  if (!sos_hp || n_sections == 0 || !(crossover_freq < s->fs / 2)) {
+    if (crossover_freq != crossover_freq) return fail(IMP_ERR_INVALID, "imp_slice_set_virtual_bass: crossover frequency is NaN");
+    if (s->vb_on) {                                        // no stale virtual-bass fields
+      HIP_TRY(hipMemsetAsync(s->d_rows, 0, (size_t)B * sizeof(imp::SliceRowOut), ctx->stream));
+      HIP_TRY(hipMemsetAsync(s->d_meas, 0, (size_t)s->m_cap * sizeof(imp::SliceMeasOut), ctx->stream));
+    }
+    s->vb_on = false;
+    return IMP_OK;
+  }
+  imp::IirSos f;
+  if ((rc = iir_sos_from(sos_hp, n_sections, &f, "imp_slice_set_virtual_bass"))) return rc;
+  if (!mpbass || !ild_mpbass || !pair_on_left) return fail(IMP_ERR_INVALID, "imp_slice_set_virtual_bass: null signal or side table");
+  if (len < s->keep_cap)
+    return fail(IMP_ERR_INVALID, "imp_slice_set_virtual_bass: mpbass / ild_mpbass of %lld samples, the slice keeps up to %lld", (long long)len,
+                (long long)s->keep_cap);
+  if (!(crossover_freq > 0)) return fail(IMP_ERR_INVALID, "imp_slice_set_virtual_bass: crossover frequency must be positive");
+  if (head < -(int64_t(1) << 40) || head > (int64_t(1) << 40)) return fail(IMP_ERR_INVALID, "imp_slice_set_virtual_bass: head out of range");
+  for (int64_t i = 0; i < s->keep_cap; ++i)
+    if (!std::isfinite(mpbass[i]) || !std::isfinite(ild_mpbass[i]))
+      return fail(IMP_ERR_INVALID, "imp_slice_set_virtual_bass: non-finite synth sample %lld", (long long)i);
+  if (!s->d_vbblock) {
+    s->vb_chunks = (s->keep_cap + imp::kIirChunk - 1) / imp::kIirChunk;
+    s->vb_spans = (s->keep_cap + imp::kVbRefSpan - 1) / imp::kVbRefSpan;
+    const int64_t M = s->m_cap, C = s->vb_chunks;
+    size_t need = 0;
+    auto take = [&](size_t bytes) {
+      const size_t at = need;
+      need += (bytes + 255) & ~(size_t)255;
+      return at;
+    };
+    const size_t o_vb = take((size_t)(B * s->pitch_crop) * 4), o_end = take((size_t)(B * C) * imp::kIirState * 8),
+                 o_init = take((size_t)(B * C) * imp::kIirState * 8), o_part = take((size_t)(B * C) * 16),
+                 o_refp = take((size_t)(M * s->vb_spans) * 16), o_mp = take((size_t)s->keep_cap * 8), o_ild = take((size_t)s->keep_cap * 8),
+                 o_P = take(256 * 8), o_gp = take((size_t)M * 8), o_left = take((size_t)s->n_pairs * 4), o_off = take((size_t)B * 8),
+                 o_len = take((size_t)B * 8), o_par = take((size_t)B * sizeof(imp::WindowParams)), o_bin = take((size_t)M * 8),
+                 o_rows = take((size_t)B * sizeof(imp::VbRow)), o_res = take((size_t)B * sizeof(imp::RowPeak));
+    if (hipMalloc((void**)&s->d_vbblock, need) != hipSuccess) {
+      (void)hipGetLastError();
+      s->d_vbblock = nullptr;
+      return fail(IMP_ERR_ALLOC, "imp_slice_set_virtual_bass: device allocation for %lld rows of %lld samples failed", (long long)B,
+                  (long long)s->pitch_crop);
+    }
+    char* blk = s->d_vbblock;
+    s->d_vb = (float*)(blk + o_vb);
+    s->d_vb_end = (double*)(blk + o_end);
+    s->d_vb_init = (double*)(blk + o_init);
+    s->d_vb_part = (double*)(blk + o_part);
+    s->d_vb_refp = (double*)(blk + o_refp);
+    s->d_vb_mp = (double*)(blk + o_mp);
+    s->d_vb_ild = (double*)(blk + o_ild);
+    s->d_vb_P = (double*)(blk + o_P);
+    s->d_vb_gp = (double*)(blk + o_gp);
+    s->d_vb_left = (int*)(blk + o_left);
+    s->d_vb_off = (int64_t*)(blk + o_off);
+    s->d_vb_len = (int64_t*)(blk + o_len);
+    s->d_vb_par = (imp::WindowParams*)(blk + o_par);
+    s->d_vb_bin = (long long*)(blk + o_bin);
+    s->d_vb_rows = (imp::VbRow*)(blk + o_rows);
+    s->d_vb_res = (imp::RowPeak*)(blk + o_res);
+    HIP_TRY(hipMemsetAsync(s->d_vbblock, 0, need, ctx->stream));
+  }
+  std::vector<double> P(256);
+  iir_transition(f, imp::kIirChunk, P.data());
+  std::vector<int> left((size_t)s->n_pairs);
+  for (int64_t q = 0; q < s->n_pairs; ++q) left[(size_t)q] = pair_on_left[q] ? 1 : 0;
+  HIP_TRY(hipMemcpyAsync(s->d_vb_mp, mpbass, (size_t)s->keep_cap * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(s->d_vb_ild, ild_mpbass, (size_t)s->keep_cap * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(s->d_vb_P, P.data(), 256 * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(s->d_vb_left, left.data(), left.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));             // the caller's arrays may go
+  s->vb_sos = f;
+  s->vb_xo = crossover_freq;
+  s->vb_pol = invert_polarity ? -1.0 : 1.0;
+  s->vb_head = head;
+  s->vb_on = true;
+  return IMP_OK;
+}
+
+extern "C" int imp_slice_vbass_hi_device(imp_slice* s, double* d_hi, int64_t pitch) {
+  if (!s) return fail(IMP_ERR_INVALID, "imp_slice_vbass_hi_device: null slice");
+  IMP_CTX_LOCK(s->ctx);
+  if (d_hi && pitch < s->keep_cap)
+    return fail(IMP_ERR_INVALID, "imp_slice_vbass_hi_device: pitch %lld < keep_cap %lld", (long long)pitch, (long long)s->keep_cap);
+  s->d_vb_hi = d_hi;
+  s->vb_hi_pitch = d_hi ? pitch : 0;
+  return IMP_OK;
+}
+
+// the virtual-bass stage of M measurements: the cropped rows materialised (crop_tails' truncation + fade-out, as the staged
+// imp_apply_window_device), their first peaks, the IIR scan with the crossover bin's DFT, the gain, hi + synth in place
+static int slice_vbass_run(imp_slice* s, hipStream_t st, int64_t M, const float* rows_al, const int64_t* off_al) {
+  const int64_t R = s->R, B = M * R, C = s->vb_chunks;
+  hipLaunchKernelGGL(imp::vbass_tables_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, (const long long*)s->d_keep, (int)R, (int)B,
+                     (long long)s->pitch_crop, (long long)s->fade_out, s->fs, s->vb_xo, s->d_vb_off, s->d_vb_len, s->d_vb_par, s->d_vb_bin);
+  hipLaunchKernelGGL(imp::apply_window_copy_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (s->keep_cap + 1023) / 1024)), (unsigned)B),
+                     dim3(256), 0, st, rows_al, off_al, s->d_vb, (const int64_t*)s->d_vb_off, (const int64_t*)s->d_vb_len,
+                     (const imp::WindowParams*)s->d_vb_par);
+  hipLaunchKernelGGL(imp::row_chunk_max_kernel, dim3((unsigned)s->knee_chunks, (unsigned)B), dim3(256), 0, st, (const float*)s->d_vb,
+                     (const int64_t*)s->d_vb_off, (const int64_t*)s->d_vb_len, (int64_t)0, s->d_chunk, s->knee_chunks);
+  hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)B), dim3(imp::kPeakThreads), 0, st, (const float*)s->d_vb,
+                     (const int64_t*)s->d_vb_off, (const int64_t*)s->d_vb_len, (int64_t)0, (const unsigned*)nullptr, 0, (const unsigned*)s->d_chunk,
+                     s->knee_chunks, s->d_vb_res, s->peak_height, (long long*)nullptr);
+  HIP_TRY(hipGetLastError());
+  const dim3 grid((unsigned)((C + 63) / 64), (unsigned)B);
+  hipLaunchKernelGGL(imp::iir_chunk_end_kernel<float>, grid, dim3(64), 0, st, s->vb_sos, (const float*)s->d_vb, (const int64_t*)s->d_vb_off,
+                     (const int64_t*)s->d_vb_len, s->d_vb_end, (long long)C);
+  hipLaunchKernelGGL(imp::iir_carry_kernel, dim3((unsigned)B), dim3(64), 0, st, (const double*)s->d_vb_P, (const int64_t*)s->d_vb_len,
+                     (const double*)s->d_vb_end, s->d_vb_init, (long long)C);
+  hipLaunchKernelGGL(imp::vbass_ref_dft_kernel, dim3((unsigned)s->vb_spans, (unsigned)M), dim3(256), 0, st, (const double*)s->d_vb_mp,
+                     (const long long*)s->d_keep, (const long long*)s->d_vb_bin, s->d_vb_refp, (int)s->vb_spans);
+  hipLaunchKernelGGL(imp::vbass_dft_kernel, grid, dim3(64), 0, st, s->vb_sos, (const float*)s->d_vb, (const int64_t*)s->d_vb_off,
+                     (const int64_t*)s->d_vb_len, (const double*)s->d_vb_init, (long long)C, (const long long*)s->d_vb_bin, (int)R, s->d_vb_part);
+  hipLaunchKernelGGL(imp::vbass_gain_kernel, dim3((unsigned)M), dim3(256), 0, st, (const double*)s->d_vb_part, (long long)C,
+                     (const double*)s->d_vb_refp, (int)s->vb_spans, (const long long*)s->d_keep, (const long long*)s->d_vb_bin,
+                     (const imp::RowPeak*)s->d_vb_res, (const int*)s->d_vb_left, (int)R, (long long)s->vb_head, s->vb_pol, s->d_vb_gp,
+                     s->d_vb_rows, s->d_rows, s->d_meas, s->d_flags);
+  hipLaunchKernelGGL(imp::vbass_synth_kernel, grid, dim3(64), 0, st, s->vb_sos, s->d_vb, (const int64_t*)s->d_vb_off, (const int64_t*)s->d_vb_len,
+                     (const double*)s->d_vb_init, (long long)C, (int)R, (const double*)s->d_vb_gp, (const imp::VbRow*)s->d_vb_rows,
+                     (const double*)s->d_vb_mp, (const double*)s->d_vb_ild, s->d_vb_hi, (long long)s->vb_hi_pitch);
+  HIP_TRY(hipGetLastError());
+  return IMP_OK;
+}
+
 // K1 of one measurement: the pairs in runs of equal spacing, a run in launch groups of at most the plan's capacity
 template <class Sample>
 static int slice_ingest_typed(imp_slice* s, const Sample* rec, int64_t m, float scale) {
@@ -542,12 +694,22 @@ extern "C" int imp_slice_execute_device(imp_slice* s, const void* d_rec, int64_t
                      off_al, (const int64_t*)s->d_len2, (int)R, (int)M, (long long)s->fade_out, (long long)s->keep_cap,
                      (long long)s->taps, s->d_keep, s->d_outlen, s->d_rows, s->d_meas, s->d_flags);
   HIP_TRY(hipGetLastError());
+  // ---- virtual bass (core/pipeline.py:603-616): the cropped rows high-passed at the crossover plus the synthesised bass
+  const float* rows_eq = rows_al;
+  const int64_t* off_eq = off_al;
+  long long fade_eq = s->fade_out;
+  if (s->vb_on) {
+    if ((rc = slice_vbass_run(s, st, M, rows_al, off_al))) return rc;
+    rows_eq = s->d_vb;                                     // truncated and faded already: K5 reads them as they are
+    off_eq = s->d_vb_off;
+    fade_eq = 0;
+  }
   // ---- equalize: K5 over every row, straight from the deconvolved columns - offsets, lengths and the fade-out from the device
   {
     imp_plan* f = s->fir;
     f->cur_stream = st;
-    imp::LoadRowsDeviceLen ld{rows_al, off_al, (const long long*)s->d_keep, (int)R, (long long)s->taps,
-                              (long long)s->fade_out, (const double*)s->d_win};
+    imp::LoadRowsDeviceLen ld{rows_eq, off_eq, (const long long*)s->d_keep, (int)R, (long long)s->taps,
+                              fade_eq, (const double*)s->d_win};
     if ((rc = launch_fir_block(f, ld, B, d_out, out_pitch, 0))) return rc;
   }
   // ---- adjust decay: decay_params + decay_times of the equalized rows that have a target, the window in place

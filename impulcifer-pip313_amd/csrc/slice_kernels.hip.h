@@ -24,6 +24,7 @@ enum {
                              // TypeError), or a knee before the window's start (ValueError): the host flow decides / raises
   SLICE_ALIGN_GUARD = 256,   // alignment: a row shorter than the correlation segment, an all-zero row, or a delayed row whose
                              // first sample is not zero (the host flow decides on the materialised rows)
+  SLICE_VBASS_GUARD = 512,   // virtual bass: a gain or crossover magnitude that is zero or not finite, or a zero denominator
 };
 
 struct SliceRowOut {         // per row, returned to the host at the end (imp_slice_row_result)
@@ -41,6 +42,8 @@ struct SliceRowOut {         // per row, returned to the host at the end (imp_sl
   int decay_flags;           // KNEE_* of that search
   long long shift_ipsilateral;   // alignment (imp_slice_set_alignment): samples align_ipsilateral_all delayed the row by (>= 0) ...
   long long shift_onset;         // ... and the signed shift align_onset_groups_peak_leftref gave it afterwards
+  long long vbass_itd;           // virtual bass (imp_slice_set_virtual_bass): peak(right) - peak(left) of the pair's cropped rows ...
+  double vbass_mag;              // ... and |rfft(hi)[k]| of this row at the crossover bin
 };
 
 struct SliceMeasOut {        // per measurement (imp_slice_result)
@@ -50,6 +53,8 @@ struct SliceMeasOut {        // per measurement (imp_slice_result)
   double gain_db;            // what normalize returns
   float gain;                // 10^(gain_db / 20) as applied (fp32 rows)
   int flags;                 // SLICE_*
+  double vbass_gain;         // virtual bass: mean |hi[k]| / (|rfft(mpbass[:keep])[k]| + 1e-20), before the polarity
+  long long vbass_bin;       // ... and the crossover bin k
 };
 
 // ---- crop_heads -------------------------------------------------------------------------------------------------------

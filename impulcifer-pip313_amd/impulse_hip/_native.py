@@ -65,18 +65,19 @@ class SliceRowResult(C.Structure):
     _fields_ = [("peak", C.c_int64), ("cut", C.c_int64), ("len", C.c_int64), ("knee", C.c_int64),
                 ("knee_flags", C.c_int32), ("knee_why", C.c_int32), ("decay_peak", C.c_int64), ("decay_knee", C.c_int64),
                 ("decay_slope", C.c_double), ("decay_level_db", C.c_double), ("decay_state", C.c_int32), ("decay_flags", C.c_int32),
-                ("shift_ipsilateral", C.c_int64), ("shift_onset", C.c_int64)]
+                ("shift_ipsilateral", C.c_int64), ("shift_onset", C.c_int64), ("vbass_itd", C.c_int64), ("vbass_mag", C.c_double)]
 
 
 class SliceResult(C.Structure):
     _fields_ = [("keep", C.c_int64), ("out_len", C.c_int64), ("peak_db", C.c_double * 2), ("gain_db", C.c_double),
-                ("gain", C.c_float), ("flags", C.c_int32)]
+                ("gain", C.c_float), ("flags", C.c_int32), ("vbass_gain", C.c_double), ("vbass_bin", C.c_int64)]
 
 
 (SLICE_KNEE_GUARD, SLICE_KNEE_RANGE, SLICE_KEEP_CAP, SLICE_FADE, SLICE_GAIN_GUARD, SLICE_GAIN_NONFINITE, SLICE_SHORT, SLICE_DECAY_GUARD,
- SLICE_ALIGN_GUARD) = (1, 2, 4, 8, 16, 32, 64, 128, 256)
+ SLICE_ALIGN_GUARD, SLICE_VBASS_GUARD) = (1, 2, 4, 8, 16, 32, 64, 128, 256, 512)
 SLICE_REDO = (SLICE_KNEE_GUARD | SLICE_KNEE_RANGE | SLICE_KEEP_CAP | SLICE_FADE | SLICE_GAIN_GUARD | SLICE_GAIN_NONFINITE
-              | SLICE_DECAY_GUARD | SLICE_ALIGN_GUARD)
+              | SLICE_DECAY_GUARD | SLICE_ALIGN_GUARD | SLICE_VBASS_GUARD)
+IIR_CHUNK = 128                                            # IMP_IIR_CHUNK: samples per chunk of imp_sosfilt_chunked
 
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -128,6 +129,8 @@ SIGNATURES = {
     "imp_slice_execute_device": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64]),
     "imp_slice_results": (C.c_int, [_vp, C.POINTER(SliceRowResult), C.POINTER(SliceResult)]),
     "imp_slice_set_decay": (C.c_int, [_vp, _pd]),
+    "imp_slice_set_virtual_bass": (C.c_int, [_vp, _pd, _i64, _pd, _pd, _i64, C.c_double, _i64, C.c_int32, C.POINTER(C.c_int32)]),
+    "imp_slice_vbass_hi_device": (C.c_int, [_vp, _vp, _i64]),
     "imp_slice_set_alignment": (C.c_int, [_vp, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, _i64]),
     "imp_xcorr_argmax_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _pi64, _pi64, _i64, _pi64, _pd]),
     "imp_shift_rows_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _pi64, _i64, _vp, _pi64]),
@@ -160,6 +163,7 @@ SIGNATURES = {
     "imp_decay_times": (C.c_int, [_vp, _pd, _pi64, _pi64, _i64, _pi64, _pi64, _pd, _pi64, C.c_double, _pd]),
     "imp_decay_times_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, _pi64, _pi64, _pd, _pi64, C.c_double, _pd]),
     "imp_sosfilt": (C.c_int, [_vp, _pd, _i64, _pd, _pi64, _pi64, _i64, _pd]),
+    "imp_sosfilt_chunked": (C.c_int, [_vp, _pd, _i64, _pd, _pi64, _pi64, _i64, _pd]),
     "imp_xcorr_argmax": (C.c_int, [_vp, _pd, _pi64, _pi64, _pd, _pi64, _pi64, _i64, _pi64, _pd]),
     "imp_minphase_fir": (C.c_int, [_vp, _pd, _i64, _i64, C.c_double, _pd]),
     "imp_curves_create": (C.c_int, [_vp, _pd, _i64, C.POINTER(_vp)]),
@@ -482,8 +486,11 @@ class Context:
                                                     nf.ctypes.data_as(_pd), _ptr_i64(ws), float(fs), out.ctypes.data_as(_pd)))
         return out
 
-    def sosfilt(self, sos, rows):
-        """scipy.signal.sosfilt(sos, row) for every row (fp64 on the device, bit-identical). Returns a list."""
+    def sosfilt(self, sos, rows, chunked=False):
+        """scipy.signal.sosfilt(sos, row) for every row (fp64 on the device, bit-identical). Returns a list.
+        chunked: the chunk-parallel scan of the virtual-bass stage instead (imp_sosfilt_chunked: <= 8 sections, not
+        bit-identical: within 1e-12 of the row's peak)"""
+        fn = self._lib.imp_sosfilt_chunked if chunked else self._lib.imp_sosfilt
         sos = np.ascontiguousarray(sos, dtype=np.float64).reshape(-1, 6)
         rows = [np.ascontiguousarray(r, dtype=np.float64).ravel() for r in rows]
         B = len(rows)
@@ -494,8 +501,8 @@ class Context:
         offs[1:] = np.cumsum(lens)[:-1]
         flat = np.concatenate(rows) if lens.sum() else np.zeros(1)
         out = np.zeros_like(flat)
-        _check(self._lib.imp_sosfilt(self._h, sos.ctypes.data_as(_pd), len(sos), flat.ctypes.data_as(_pd), _ptr_i64(offs),
-                                     _ptr_i64(lens), B, out.ctypes.data_as(_pd)))
+        _check(fn(self._h, sos.ctypes.data_as(_pd), len(sos), flat.ctypes.data_as(_pd), _ptr_i64(offs), _ptr_i64(lens), B,
+                  out.ctypes.data_as(_pd)))
         return [out[o:o + n].copy() for o, n in zip(offs, lens)]
 
     def xcorr_argmax(self, a_rows, b_rows):
@@ -772,6 +779,27 @@ class Slice:
         if t.shape != (self.rows,):
             raise ValueError(f"one decay target per row of a measurement ({self.rows}), got {t.shape}")
         _check(self._lib.imp_slice_set_decay(self._h, t.ctypes.data_as(_pd)))
+
+    def set_virtual_bass(self, sos_hp, mpbass, ild_mpbass, crossover_freq, head, invert_polarity, pair_on_left):
+        """the virtual-bass stage between crop_tails and equalize (imp_slice_set_virtual_bass); sos_hp None switches it off"""
+        if sos_hp is None:
+            _check(self._lib.imp_slice_set_virtual_bass(self._h, None, 0, None, None, 0, 0.0, 0, 0, None))
+            return
+        sos = np.ascontiguousarray(sos_hp, dtype=np.float64).reshape(-1, 6)
+        mp = np.ascontiguousarray(mpbass, dtype=np.float64)
+        ild = np.ascontiguousarray(ild_mpbass, dtype=np.float64)
+        left = np.ascontiguousarray(pair_on_left, dtype=np.int32)
+        if mp.shape != ild.shape or mp.ndim != 1:
+            raise ValueError("mpbass and ild_mpbass: one signal each, of one length")
+        if left.shape != (self.rows // 2,):
+            raise ValueError(f"one side flag per ear pair ({self.rows // 2}), got {left.shape}")
+        _check(self._lib.imp_slice_set_virtual_bass(self._h, sos.ctypes.data_as(_pd), len(sos), mp.ctypes.data_as(_pd),
+                                                    ild.ctypes.data_as(_pd), len(mp), float(crossover_freq), int(head),
+                                                    int(bool(invert_polarity)), left.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def vbass_hi_device(self, d_hi, pitch=0):
+        """test hook: the next calls also leave the fp64 high-passed rows at d_hi ([M * rows][pitch]); None stops it"""
+        _check(self._lib.imp_slice_vbass_hi_device(self._h, _vp(int(d_hi)) if d_hi else None, int(pitch)))
 
     def pack_f64(self, d_out, out_pitch, M, d_packed, meas_stride):
         """the last call's rows as float64, every measurement packed as a [rows][out_len] array (asynchronous)"""

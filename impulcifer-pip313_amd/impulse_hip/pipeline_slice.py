@@ -53,7 +53,7 @@ def _expected_tasks(recordings):
 
 
 def run_slice(estimator, recordings, room_frs=None, target=None, head_ms=1, decay=None, peak_target=-0.1,
-              hp_left=None, hp_right=None, eq_left=None, eq_right=None, stages=None, firs=None, align=False):
+              hp_left=None, hp_right=None, eq_left=None, eq_right=None, stages=None, firs=None, align=False, vbass=None):
     """recordings: list of (path_or_(fs, array), speakers[, side]) measurement files.
     Returns the HRIR after: ingest (batched GPU deconvolution) -> crop_heads -> crop_tails ->
     per-channel minimum-phase FIR (batched GPU design) + equalize -> optional decay adjustment ->
@@ -65,7 +65,9 @@ def run_slice(estimator, recordings, room_frs=None, target=None, head_ms=1, deca
     no design runs then.
     ``align``: run the two alignments `_stage_crop_and_align` has between crop_heads and crop_tails (core/pipeline.py:593-597:
     align_ipsilateral_all over IPSILATERAL_PAIRS with 30 ms segments, align_onset_groups_peak_leftref); responses that are
-    on the device stay there."""
+    on the device stay there.
+    ``vbass``: None, or the keywords of virtual_bass.apply_virtual_bass_to_hrir (crossover_freq, head_ms, hp_freq,
+    invert_polarity): virtual bass between crop_tails and equalize, where the reference runs it (core/pipeline.py:603-616)."""
     hrir = HRIR(estimator)
     fs = estimator.fs
     common = FrequencyResponse.generate_frequencies(f_min=10, f_max=fs / 2, f_step=1.01)
@@ -98,6 +100,10 @@ def run_slice(estimator, recordings, room_frs=None, target=None, head_ms=1, deca
         snap("align")
     hrir.crop_tails()
     snap("crop_tails")
+    if vbass is not None:
+        from .virtual_bass import apply_virtual_bass_to_hrir
+        apply_virtual_bass_to_hrir(hrir, **vbass)
+        snap("vbass")
 
     tasks = [(sp, sd) for sp, pair in hrir.irs.items() for sd in pair]
     if firs is None:
@@ -124,14 +130,14 @@ def run_slice(estimator, recordings, room_frs=None, target=None, head_ms=1, deca
 
 
 def run_measurement_dirs(estimator, dir_paths, room_frs=None, target=None, head_ms=1, decay=None, peak_target=-0.1,
-                         hp_left=None, hp_right=None, eq_left=None, eq_right=None, align=True):
+                         hp_left=None, hp_right=None, eq_left=None, eq_right=None, align=True, vbass=None):
     """The same stage sequence for MANY measurement directories of one layout (a listener measured again, a room measured at
     several seats), each laid out as `open_binaural_measurements` reads it (core/pipeline_stages.py:504-522: `<speaker
     list>.wav` files): the equalisation FIRs are designed once (the curves belong to the job), the recordings are read,
     uploaded, run through the device-resident sequence (imp_slice) and brought back as overlapping stages - one pipeline
     per device of IMPULSE_HIP_DEVICES.  Returns [(HRIR, gain dB)] in the order of dir_paths; every result is what
     run_slice gives for that directory with the same arguments (align defaults to True here: the reference's flow runs
-    the two alignments between crop_heads and crop_tails)."""
+    the two alignments between crop_heads and crop_tails; vbass as run_slice)."""
     from .resident_slice import WavMeasurements, run_slice_jobs
     job, speakers = WavMeasurements.from_dirs(dir_paths, fs=estimator.fs)
     layout = job.layout(estimator, speakers)
@@ -141,4 +147,5 @@ def run_measurement_dirs(estimator, dir_paths, room_frs=None, target=None, head_
         target = FrequencyResponse(name="target", frequency=common.copy(), raw=0)
     firs = {(sp, sd): fir for sp, sd, fir in process_equalization_batch(layout.tasks, room_frs, hp_left, hp_right, eq_left, eq_right,
                                                                         target, common, fs, on_device=True)}
-    return run_slice_jobs(estimator, layout, job, firs, head_ms=head_ms, peak_target=peak_target, decay=decay, align=align)
+    return run_slice_jobs(estimator, layout, job, firs, head_ms=head_ms, peak_target=peak_target, decay=decay, align=align,
+                          vbass=vbass)

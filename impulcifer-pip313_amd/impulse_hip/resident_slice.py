@@ -191,6 +191,9 @@ class ResidentSlice:
         self.firs = None
         self.decay = None
         self.align = False
+        self.vbass = None
+        self._vb_key = None
+        self._vb_designs = {}                              # (crossover, hp_freq, length) -> (sos, mpbass, ild_mpbass)
         self.slice = None
         self.stats = dict(measurements=0, staged=0, regrown=0)
         self._make(self._cap_for(int(1.1 * fs)) if keep_cap is None else int(keep_cap))
@@ -216,6 +219,9 @@ class ResidentSlice:
             self.set_decay(self.decay)
         if self.align:
             self.set_alignment(True)
+        if self.vbass is not None:
+            self._vb_key = None
+            self.set_virtual_bass(**self.vbass)
 
     def set_alignment(self, on=True):
         """the alignments `_stage_crop_and_align` runs between crop_heads and crop_tails (core/pipeline.py:593-597):
@@ -240,6 +246,32 @@ class ResidentSlice:
         else:
             per_row = [float(decay)] * len(self.layout.tasks)
         self.slice.set_decay(per_row)
+
+    def set_virtual_bass(self, crossover_freq=250, head_ms=1.0, hp_freq=15.0, invert_polarity=None):
+        """the optional stage between crop_tails and equalize (core/pipeline.py:603-616 -> core/virtual_bass.py:82-176):
+        every cropped row high-passed at the crossover plus the synthesised bass, gain-matched at the crossover bin - on the
+        device (imp_slice_set_virtual_bass).  crossover_freq None switches the stage off; so does a crossover at or above
+        fs / 2, where the reference leaves the responses as they are.  The filter designs are made here, once per options."""
+        opts = vbass_options(self.fs, crossover_freq, head_ms, hp_freq, invert_polarity)
+        if opts is None or opts["crossover_freq"] >= self.fs / 2:
+            self.vbass = opts
+            self._vb_key = None
+            self.slice.set_virtual_bass(None, None, None, 0, 0, False, None)
+            return
+        key = (opts["crossover_freq"], opts["head_ms"], opts["hp_freq"], bool(opts["invert_polarity"]), self.keep_cap, id(self.slice))
+        self.vbass = opts
+        if key == self._vb_key:                              # same options, same slice: the designs are on the device already
+            return
+        dkey = (opts["crossover_freq"], opts["hp_freq"], self.keep_cap)
+        if dkey not in self._vb_designs:                     # designed once per options: a job that switches it on again uploads
+            from .virtual_bass import slice_designs
+            with _native.using_context(self.ctx):
+                self._vb_designs[dkey] = slice_designs(self.fs, self.keep_cap, opts["crossover_freq"], opts["hp_freq"])
+        sos, mp, ild = self._vb_designs[dkey]
+        left = [speaker_side(sp) == "left" for sp in self.layout.speakers]
+        head = int(round(opts["head_ms"] * 1e-3 * self.fs))
+        self.slice.set_virtual_bass(sos, mp, ild, opts["crossover_freq"], head, bool(opts["invert_polarity"]), left)
+        self._vb_key = key
 
     def grow_for(self, rows):
         """After a call that flagged IMP_SLICE_KEEP_CAP: size the slice for the crop_tails lengths those rows ask for (the
@@ -379,7 +411,7 @@ class ResidentSlice:
             def staged(m, batch=batch):
                 jobs = [((self.fs, np.asarray(fr)), spec[2], None) for fr, spec in zip(batch[m], self.layout.files)]
                 return run_slice(self.estimator, jobs, head_ms=self.head_ms, peak_target=self.peak_target, firs=self.firs_by_task(),
-                                 decay=self.decay, align=self.align)
+                                 decay=self.decay, align=self.align, vbass=self.vbass)
 
             results.extend(self.collect(block, batch, staged))
         return results
@@ -449,6 +481,7 @@ class SliceRunner:
                     rs.set_firs(job["firs"])
                     rs.set_decay(job["decay"])
                     rs.set_alignment(job["align"])
+                    _set_vbass(rs, job["vbass"])
                     while True:
                         with self._lock:
                             i = job["next"]
@@ -471,7 +504,7 @@ class SliceRunner:
                         def staged(m, recs=recs):
                             jobs = [((est.fs, np.asarray(fr)), spec[2], None) for fr, spec in zip(recs, layout.files)]
                             return run_slice(est, jobs, head_ms=self.head_ms, peak_target=self.peak_target, firs=job["firs"],
-                                             decay=job["decay"], align=job["align"])
+                                             decay=job["decay"], align=job["align"], vbass=job["vbass"])
 
                         if not host:
                             res = rs.collect(block, [recs], staged)[0]
@@ -525,12 +558,15 @@ class SliceRunner:
         rs.slice.pack_f64(ln["d_out"], rs.out_pitch, 1, ln["d_packed"], R * cap)
         return None
 
-    def run(self, measurements, firs, to_host=True, decay=None, align=False):
+    def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None):
         """[(HRIR, gain dB)] in the order of `measurements` ([[frames of file 0, ...], ...]).  firs: {(speaker, side):
         taps}, designed once per job (the curves belong to the job, core/pipeline.py:668-688).  to_host: True = the
         responses as float64 host arrays (as the reference's classes hold them), converted inside the workers;
-        False = left on the device.  decay: as ResidentSlice.set_decay; align: as ResidentSlice.set_alignment."""
-        job = dict(measurements=measurements, firs=firs, to_host=to_host, decay=decay, align=align, next=0, out=[None] * len(measurements))
+        False = left on the device.  decay: as ResidentSlice.set_decay; align: as ResidentSlice.set_alignment; vbass: None
+        or the keywords of ResidentSlice.set_virtual_bass."""
+        _check_vbass(self.estimator.fs, vbass)
+        job = dict(measurements=measurements, firs=firs, to_host=to_host, decay=decay, align=align, vbass=vbass, next=0,
+                   out=[None] * len(measurements))
         lanes = self.lanes[:max(1, min(len(self.lanes), len(measurements)))]
         with self._run_lock:                               # one job at a time: the lanes' completion markers carry no job identity
             for ln in lanes:
@@ -698,6 +734,7 @@ class SlicePipeline:
                     rs.set_firs(_firs_for(job["firs"], layout, ctx))
                     rs.set_decay(job["decay"])
                     rs.set_alignment(job["align"])
+                    _set_vbass(rs, job["vbass"])
                 except BaseException as exc:               # noqa: BLE001
                     self._fail(job, exc)
                 for _ in range(len(job["measurements"])):
@@ -734,7 +771,7 @@ class SlicePipeline:
                             rs.stats["staged"] += 1
                             jobs = [((est.fs, np.asarray(fr)), spec[2], None) for fr, spec in zip(recs, layout.files)]
                             res = run_slice(est, jobs, head_ms=self.head_ms, peak_target=self.peak_target, firs=job["firs"],
-                                            decay=job["decay"], align=job["align"])
+                                            decay=job["decay"], align=job["align"], vbass=job["vbass"])
                             if host:
                                 res[0].to_host()
                             out = ("result", res)
@@ -794,14 +831,15 @@ class SlicePipeline:
                     job["done"].set()
         ctx.close()
 
-    def run(self, measurements, firs, to_host=True, decay=None, align=False):
-        """[(HRIR, gain dB)] in the order of `measurements` ([[frames of file 0, ...], ...]); firs, to_host, decay and align
-        as SliceRunner.run"""
+    def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None):
+        """[(HRIR, gain dB)] in the order of `measurements` ([[frames of file 0, ...], ...]); firs, to_host, decay, align and
+        vbass as SliceRunner.run"""
+        _check_vbass(self.estimator.fs, vbass)
         if not len(measurements):
             return []
         import threading
-        job = dict(measurements=measurements, firs=firs, to_host=to_host, decay=decay, align=align, out=[None] * len(measurements),
-                   left=len(measurements), error=None, done=threading.Event())
+        job = dict(measurements=measurements, firs=firs, to_host=to_host, decay=decay, align=align, vbass=vbass,
+                   out=[None] * len(measurements), left=len(measurements), error=None, done=threading.Event())
         with self._submit:                                 # jobs of concurrent callers enter both stage queues in one order
             for q in self.jobs:
                 q.put(job)
@@ -851,18 +889,18 @@ class SliceFleet:
             self.close()
             raise
 
-    def run(self, measurements, firs, to_host=True, decay=None, align=False):
+    def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None):
         from concurrent.futures import ThreadPoolExecutor
         from .sharding import shard_channels
         n = len(measurements)
         blocks = [(k,) + shard_channels(n, len(self.pipes), k, keep_pairs=False) for k in range(len(self.pipes))]
         blocks = [(k, lo, hi) for k, lo, hi in blocks if hi > lo]
         if len(blocks) <= 1:
-            return self.pipes[0].run(measurements, firs, to_host=to_host, decay=decay, align=align) if n else []
+            return self.pipes[0].run(measurements, firs, to_host=to_host, decay=decay, align=align, vbass=vbass) if n else []
 
         def part(item):
             k, lo, hi = item
-            return self.pipes[k].run(measurements[lo:hi], firs, to_host=to_host, decay=decay, align=align)
+            return self.pipes[k].run(measurements[lo:hi], firs, to_host=to_host, decay=decay, align=align, vbass=vbass)
 
         with ThreadPoolExecutor(max_workers=len(blocks), thread_name_prefix="impulse-fleet") as pool:
             parts = list(pool.map(part, blocks))
@@ -885,7 +923,8 @@ class _Skip(Exception):
     """a measurement of a job that has already failed: passed through the stages untouched"""
 
 
-def run_slice_jobs(estimator, layout, measurements, firs, workers=None, head_ms=1, peak_target=-0.1, decay=None, align=False):
+def run_slice_jobs(estimator, layout, measurements, firs, workers=None, head_ms=1, peak_target=-0.1, decay=None, align=False,
+                   vbass=None):
     """one job through a runner made for it (responses on the host): a three-stage SlicePipeline per device of
     IMPULSE_HIP_DEVICES (SliceFleet), or with `workers` that many SliceRunner lanes; callers with several jobs keep a runner"""
     if workers is None:
@@ -893,9 +932,52 @@ def run_slice_jobs(estimator, layout, measurements, firs, workers=None, head_ms=
     else:
         runner = SliceRunner(estimator, layout, workers=workers, head_ms=head_ms, peak_target=peak_target)
     try:
-        return runner.run(measurements, firs, to_host=True, decay=decay, align=align)
+        return runner.run(measurements, firs, to_host=True, decay=decay, align=align, vbass=vbass)
     finally:
         runner.close()
+
+
+def vbass_options(fs, crossover_freq=250, head_ms=1.0, hp_freq=15.0, invert_polarity=None):
+    """the options of the virtual-bass stage checked and normalised (None: off), refused with the reason before anything
+    runs"""
+    import numbers
+    if crossover_freq is None:
+        return None
+
+    def real(name, v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real) or not np.isfinite(float(v)):
+            raise ValueError(f"virtual bass: {name} must be a finite number, got {v!r}")
+        return float(v)
+
+    xo, head, hp = real("crossover_freq", crossover_freq), real("head_ms", head_ms), real("hp_freq", hp_freq)
+    if xo <= 0:
+        raise ValueError(f"virtual bass: crossover_freq must be positive, got {crossover_freq!r}")
+    if not 0 < hp < fs / 2:
+        raise ValueError(f"virtual bass: hp_freq must lie in (0, fs / 2 = {fs / 2}), got {hp_freq!r}")
+    if abs(head) > 1e6:
+        raise ValueError(f"virtual bass: head_ms of {head_ms!r} is out of range")
+    if invert_polarity is not None and not isinstance(invert_polarity, (bool, np.bool_)):
+        raise ValueError(f"virtual bass: invert_polarity must be None, True or False, got {invert_polarity!r}")
+    return dict(crossover_freq=crossover_freq, head_ms=head_ms, hp_freq=hp_freq, invert_polarity=invert_polarity)
+
+
+def _check_vbass(fs, vbass):
+    """a runner's `vbass` argument (None or the keywords of set_virtual_bass), refused in the caller's thread"""
+    if vbass is None:
+        return
+    if not isinstance(vbass, dict):
+        raise ValueError(f"vbass must be None or a dict of set_virtual_bass keywords, got {type(vbass).__name__}")
+    unknown = set(vbass) - {"crossover_freq", "head_ms", "hp_freq", "invert_polarity"}
+    if unknown:
+        raise ValueError(f"vbass: unknown options {sorted(unknown)}")
+    vbass_options(fs, **vbass)
+
+
+def _set_vbass(rs, vbass):
+    if vbass is None:
+        rs.set_virtual_bass(None)
+    else:
+        rs.set_virtual_bass(**vbass)
 
 
 def _fir_taps(fs):

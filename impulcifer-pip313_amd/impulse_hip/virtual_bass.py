@@ -106,5 +106,25 @@ def synthesize_virtual_bass(irs, fs, crossover_freq=250, head_ms=1.0, hp_freq=15
         pair["right"].data = highs[2 * i + 1] + (cross if on_left else direct)
 
 
+def slice_designs(fs, length, crossover_freq=250, hp_freq=15.0, sosfilt=None):
+    """The host side of the resident stage (imp_slice_set_virtual_bass): (sos_hp8_xo, mpbass, ild_mpbass) for rows of up to
+    `length` samples, built as synthesize_virtual_bass builds them (reference :100-123).  Both signals are causal, so their
+    first n samples are exactly what the reference builds at length n.  sosfilt(sos, [row]) -> [row]: K11 by default
+    (bit-identical to scipy.signal.sosfilt)."""
+    from scipy import signal
+    if sosfilt is None:
+        sosfilt = _native.default_context().sosfilt
+    imp = np.zeros(int(length))
+    imp[0] = 1.0
+    sos_hp4_sub = signal.butter(4, hp_freq / (fs / 2), btype="high", output="sos")
+    sos_lp8_xo = _duplicate_sos(signal.butter(4, crossover_freq / (fs / 2), btype="low", output="sos"), 2)
+    mpbass = np.asarray(sosfilt(sos_lp8_xo, sosfilt(sos_hp4_sub, [imp]))[0], dtype=np.float64)
+    sos_ild = np.vstack([_rbj_high_shelf(fc, fs, g, q) for fc, g, q in ((150.0, -1.5, 0.760), (400.0, -3.0, 0.660),
+                                                                         (800.0, -3.5, 0.610))])
+    ild_mpbass = np.asarray(sosfilt(sos_ild, [mpbass])[0], dtype=np.float64)
+    sos_hp8_xo = _duplicate_sos(signal.butter(4, crossover_freq / (fs / 2), btype="high", output="sos"), 2)
+    return sos_hp8_xo, mpbass, ild_mpbass
+
+
 def apply_virtual_bass_to_hrir(hrir, crossover_freq=250, head_ms=1.0, hp_freq=15.0, invert_polarity=None):
     synthesize_virtual_bass(hrir.irs, hrir.fs, crossover_freq, head_ms, hp_freq, invert_polarity)

@@ -304,6 +304,14 @@ int imp_curves_equalization_fir_device(imp_curves* c, const double* error, int64
  */
 int imp_sosfilt(imp_ctx* ctx, const double* sos, int64_t n_sections, const double* x, const int64_t* off,
                 const int64_t* len, int64_t B, double* y);
+/* The same cascade as a chunk-parallel scan (K13, the virtual-bass stage's filter): rows cut into chunks of IMP_IIR_CHUNK
+ * samples, every chunk filtered from zero state, the chunks' initial states carried over by P = A^IMP_IIR_CHUNK (the
+ * cascade's 16 x 16 state transition, made on the host), every chunk filtered again from its true state.  1 .. 8 sections,
+ * B <= 65535 rows, same layout as imp_sosfilt.  fp64 with fused multiply-adds and a reassociated recurrence: NOT
+ * bit-identical to scipy.signal.sosfilt; within 1e-12 of the row's peak for the stable cascades tested. */
+#define IMP_IIR_CHUNK 128
+int imp_sosfilt_chunked(imp_ctx* ctx, const double* sos, int64_t n_sections, const double* x, const int64_t* off,
+                        const int64_t* len, int64_t B, double* y);
 
 /* ---- K10: lag search of the ipsilateral alignment ----------------------------------------------
  * core/hrir.py:934-937 and :946-949 (HRIR.align_ipsilateral_all):
@@ -485,6 +493,8 @@ int imp_debug_chain_tail_geometry(int64_t M, int64_t L, int64_t* history, int64_
 #define IMP_SLICE_SHORT 64          /* informational: a pair shorter than the head fade kept its head un-faded */
 #define IMP_SLICE_ALIGN_GUARD 256   /* alignment: a row shorter than the correlation segment, an all-zero row, or a delayed row
                                      * whose first sample is not zero: the host flow decides on the materialised rows */
+#define IMP_SLICE_VBASS_GUARD 512   /* virtual bass: a crossover magnitude or gain that is not finite or is zero, or a zero
+                                     * denominator: the host flow decides */
 #define IMP_SLICE_DECAY_GUARD 128   /* decay adjustment: a knee search in its guard band, no decay time defined, or a knee
                                      * before the window's start (the reference raises): the host flow decides */
 typedef struct imp_slice imp_slice;
@@ -518,6 +528,9 @@ typedef struct imp_slice_row_result {
   int32_t decay_flags;           /* flags_out of imp_decay_knees_device for that search */
   int64_t shift_ipsilateral;     /* alignment (imp_slice_set_alignment): samples align_ipsilateral_all delayed the row by */
   int64_t shift_onset;           /* ... and the signed shift align_onset_groups_peak_leftref gave it afterwards */
+  int64_t vbass_itd;             /* virtual bass (imp_slice_set_virtual_bass): peak_index(right) - peak_index(left) of the pair's
+                                  * rows after crop_tails ... */
+  double vbass_mag;              /* ... and |rfft(hi)[k]| of this row at the crossover bin k */
 } imp_slice_row_result;
 typedef struct imp_slice_result {
   int64_t keep;                  /* crop_tails' return value */
@@ -526,6 +539,8 @@ typedef struct imp_slice_result {
   double gain_db;                /* normalize's return value */
   float gain;                    /* 10^(gain_db / 20) as applied */
   int32_t flags;                 /* IMP_SLICE_* */
+  double vbass_gain;             /* virtual bass: mean |hi[k]| / (|rfft(mpbass[:keep])[k]| + 1e-20), before the polarity */
+  int64_t vbass_bin;             /* ... the crossover bin k */
 } imp_slice_result;
 /* deconv: a 'same' plan (mono or pair mode) of the column length on the slice's context, lanes = 1; it must outlive the slice */
 int imp_slice_create(imp_plan* deconv, const imp_slice_geometry* geometry, int64_t max_measurements, imp_slice** out);
@@ -564,6 +579,30 @@ int imp_slice_set_alignment(imp_slice* slice, int64_t n_ipsi, const int32_t* ips
  * knee search has a decision inside its guard band, the measurement is flagged IMP_SLICE_DECAY_GUARD.  Bit-identical to
  * imp_decay_knees_device -> imp_decay_times_device -> imp_apply_window_device on the same rows.  Drains the stream. */
 int imp_slice_set_decay(imp_slice* slice, const double* target_rt60);
+/* Virtual bass between crop_tails and equalize (core/pipeline.py:603-616 -> core/virtual_bass.py:82-176), on the device.
+ * The host designs the filters once (they depend on fs and the options only): sos_hp[n_sections][6] = the crossover
+ * high-pass sos_hp8_xo (SciPy's layout, a0 = 1, 1 .. 8 sections: the reference's is 4, order 8); mpbass = sosfilt(lp8_xo, sosfilt(hp4_sub, impulse)) and
+ * ild_mpbass = sosfilt(sos_ild, mpbass), both of `len` >= keep_cap samples (causal: their first n samples are what the
+ * reference builds at length n); head = round(head_ms * fs / 1000); pair_on_left[q] = speaker_side(speaker q) == "left".
+ * Per measurement, on the rows as crop_tails leaves them (keep samples, faded out):
+ *   hi = sosfilt(sos_hp, row) for every row (K13: chunk-parallel fp64 scan); k = the bin np.argmin(np.abs(rfftfreq(keep,
+ *   1 / fs) - crossover_freq)) picks; g = mean over the rows of |DFT(hi)[k]| / (|DFT(mpbass[:keep])[k]| + 1e-20) (single-bin
+ *   DFTs in fp64, angles reduced exactly as integers); per pair itd = peak_index(right) - peak_index(left) of the cropped
+ *   rows; the row on the speaker's side gets hi + g pol mpbass delayed by head, the other hi + g pol ild_mpbass delayed by
+ *   head + itd (speaker on the left) or head - itd (zero fill, no wrap; negative delays advance); rounded to fp32 for K5.
+ * NOT bit-identical to the staged path with the stage on: the scan reassociates SciPy's serial recurrence, the DFTs are
+ * not np.fft's, and the cross signal is g * ild_mpbass where the reference filters g * mpbass.  The integers (keep, peaks,
+ * ITDs, bins) are exact; hi agrees with scipy.signal.sosfilt within 1e-12 of the row's peak, g within 1e-10 relative, the final
+ * rows within 2e-6 of the row's peak (tolerances: DESIGN.md section 9).  A gain the device cannot speak for (not finite, zero,
+ * zero denominator) is flagged IMP_SLICE_VBASS_GUARD.  sos_hp = NULL / n_sections = 0, or crossover_freq >= fs / 2 (the
+ * reference returns unchanged), switches the stage off: the launch sequence is then exactly the one without it.
+ * Drains the stream. */
+int imp_slice_set_virtual_bass(imp_slice* slice, const double* sos_hp, int64_t n_sections, const double* mpbass,
+                               const double* ild_mpbass, int64_t len, double crossover_freq, int64_t head, int32_t invert_polarity,
+                               const int32_t* pair_on_left);
+/* test hook: the next calls also write the fp64 high-passed rows hi to d_hi ([M * 2 n_pairs][pitch], keep valid samples
+ * each; pitch >= keep_cap); NULL stops it */
+int imp_slice_vbass_hi_device(imp_slice* slice, double* d_hi, int64_t pitch);
 /* asynchronous on the context's stream; d_out: [M * 2 n_pairs][out_pitch] fp32, out_pitch >= keep_cap + taps - 1; row
  * m * 2 n_pairs + r holds result.out_len valid samples */
 int imp_slice_execute_device(imp_slice* slice, const void* d_rec, int64_t rec_stride, int64_t M, float* d_out,
