@@ -512,11 +512,21 @@ __global__ __launch_bounds__(256) void apply_window_copy_kernel(const float* __r
   }
 }
 
-// HRIR.write_wav on device rows (core/hrir.py:426-455 -> core/audio_io.py:82-97 -> soundfile, which turns libsndfile's
-// clipping on): out[i][t] = clip(lrint(row_t[i] * 2^31), -2^31, 2^31 - 1) >> (32 - bits), zeros for tracks without a row;
-// interleaved frames, the WAV wire order.  PCM_32 is pinned by the sweep WAVs the reference ships (tests/golden/
-// sweep_wavs.npz); see audio_io.pcm_quantise.  row_of_track[t] = row index or -1.  Samples are stored as int32 (bits 24/32)
-// or int16 (bits 16).
+// The PCM word of one sample, as the reference's writer makes it (core/audio_io.py:82-97 -> soundfile, which turns
+// libsndfile's clipping on): clip(lrint(x * 2^31), -2^31, 2^31 - 1) >> shift, shift = 32 - bits.  PCM_32 is pinned by the
+// sweep WAVs the reference ships (tests/golden/sweep_wavs.npz); see audio_io.pcm_quantise.  Every device PCM writer calls
+// this one rule (rows_to_pcm_kernel, slice_pack_pcm_kernel).
+__device__ __forceinline__ int pcm_word(float x, int shift) {
+  const double v = (double)x * 2147483648.0;                     // exact: a power-of-two scale
+  // saturate, then round half to even like lrint / np.rint (a NaN sample falls through to llrint, as in libsndfile)
+  long long q = v >= 2147483647.0 ? 2147483647ll : v <= -2147483648.0 ? -2147483648ll : llrint(v);
+  q >>= shift;                                                   // arithmetic shift: the top `bits` bits
+  return (int)q;
+}
+
+// HRIR.write_wav on device rows (core/hrir.py:426-455): out[i][t] = pcm_word(row_t[i]), zeros for tracks without a row;
+// interleaved frames, the WAV wire order.  row_of_track[t] = row index or -1.  Samples are stored as int32 (bits 24/32) or
+// int16 (bits 16).
 __global__ __launch_bounds__(256) void rows_to_pcm_kernel(const float* __restrict__ src, const int64_t* __restrict__ off,
                                                           const int64_t* __restrict__ len,
                                                           const int64_t* __restrict__ row_of_track, int n_tracks,
@@ -527,15 +537,9 @@ __global__ __launch_bounds__(256) void rows_to_pcm_kernel(const float* __restric
     const int64_t i = k / n_tracks;
     const int t = (int)(k - i * n_tracks);
     const int64_t r = row_of_track[t];
-    long long q = 0;
-    if (r >= 0 && i < len[r]) {
-      const double v = (double)src[off[r] + i] * 2147483648.0;   // exact: a power-of-two scale
-      // saturate, then round half to even like lrint / np.rint (a NaN sample falls through to llrint, as in libsndfile)
-      q = v >= 2147483647.0 ? 2147483647ll : v <= -2147483648.0 ? -2147483648ll : llrint(v);
-      q >>= shift;                                               // arithmetic shift: the top `bits` bits
-    }
+    const int q = (r >= 0 && i < len[r]) ? pcm_word(src[off[r] + i], shift) : 0;
     if (bits == 16) reinterpret_cast<short*>(out)[k] = (short)q;
-    else reinterpret_cast<int*>(out)[k] = (int)q;
+    else reinterpret_cast<int*>(out)[k] = q;
   }
 }
 

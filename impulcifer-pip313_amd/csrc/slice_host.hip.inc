@@ -791,6 +791,48 @@ extern "C" int imp_slice_pack_f64(imp_slice* s, const float* d_out, int64_t out_
   return IMP_OK;
 }
 
+// slice_pack_pcm_kernel over M measurements of R rows (pitch apart) whose lengths are on the device, at most max_len
+static int pack_pcm_launch(hipStream_t st, const float* d_rows, int64_t pitch, const long long* d_len, int64_t R, int64_t M,
+                           int64_t max_len, int bits, int32_t* d_packed, int64_t meas_stride) {
+  int64_t tile = 1;                                  // frames per workgroup: a [tile][R] block of about 16 KiB, at most 512 frames
+  while (tile < 512 && 2 * tile * R <= 4096) tile *= 2;
+  const size_t lds = (size_t)(tile * (R | 1)) * sizeof(int32_t);
+  const unsigned bx = (unsigned)std::max<int64_t>(1, (max_len + tile - 1) / tile);
+  hipLaunchKernelGGL(imp::slice_pack_pcm_kernel, dim3(bx, (unsigned)M), dim3(256), lds, st, d_rows, (long long)pitch, d_len, (int)R,
+                     (int)tile, 32 - bits, (int*)d_packed, (long long)meas_stride);
+  HIP_TRY(hipGetLastError());
+  return IMP_OK;
+}
+
+extern "C" int imp_slice_pack_pcm(imp_slice* s, const float* d_out, int64_t out_pitch, int64_t M, int bits, int32_t* d_packed,
+                                  int64_t meas_stride) {
+  if (!s || !d_out || !d_packed) return fail(IMP_ERR_INVALID, "imp_slice_pack_pcm: null argument");
+  if (bits != 16 && bits != 24 && bits != 32) return fail(IMP_ERR_INVALID, "imp_slice_pack_pcm: %d bits (16, 24 or 32)", bits);
+  IMP_CTX_LOCK(s->ctx);
+  if (M < 1 || M > s->m_cap || M != s->last_M)
+    return fail(IMP_ERR_INVALID, "imp_slice_pack_pcm: %lld measurements, the last call had %lld", (long long)M, (long long)s->last_M);
+  if (out_pitch < s->out_len_max || meas_stride < s->R * s->out_len_max)
+    return fail(IMP_ERR_INVALID, "imp_slice_pack_pcm: out_pitch %lld / meas_stride %lld too small for %lld rows of %lld", (long long)out_pitch,
+                (long long)meas_stride, (long long)s->R, (long long)s->out_len_max);
+  int rc = ctx_bind(s->ctx);
+  if (rc) return rc;
+  return pack_pcm_launch(s->ctx->stream, d_out, out_pitch, (const long long*)s->d_outlen, s->R, M, s->out_len_max, bits, d_packed,
+                         meas_stride);
+}
+
+extern "C" int imp_pack_pcm_device(imp_ctx* ctx, const float* d_rows, int64_t pitch, const int64_t* d_len, int64_t rows_per_meas,
+                                   int64_t M, int64_t max_len, int bits, int32_t* d_packed, int64_t meas_stride) {
+  if (!ctx || !d_rows || !d_len || !d_packed) return fail(IMP_ERR_INVALID, "imp_pack_pcm_device: null argument");
+  if (bits != 16 && bits != 24 && bits != 32) return fail(IMP_ERR_INVALID, "imp_pack_pcm_device: %d bits (16, 24 or 32)", bits);
+  if (rows_per_meas < 1 || rows_per_meas > 8192 || M < 1 || M > 65535 || max_len < 0 || pitch < max_len ||
+      meas_stride < rows_per_meas * max_len)
+    return fail(IMP_ERR_INVALID, "imp_pack_pcm_device: bad sizes");
+  IMP_CTX_LOCK(ctx);
+  int rc = ctx_bind(ctx);
+  if (rc) return rc;
+  return pack_pcm_launch(ctx->stream, d_rows, pitch, (const long long*)d_len, rows_per_meas, M, max_len, bits, d_packed, meas_stride);
+}
+
 extern "C" int imp_host_alloc(imp_ctx* ctx, size_t bytes, void** out) {
   if (!ctx || !out) return fail(IMP_ERR_INVALID, "imp_host_alloc: null argument");
   *out = nullptr;

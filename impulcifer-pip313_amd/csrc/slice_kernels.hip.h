@@ -493,4 +493,54 @@ __global__ void __launch_bounds__(256) slice_pack_f64_kernel(const float* __rest
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) dst[i] = (double)src[i];
 }
 
+// The finished rows as the PCM words of a WAV data chunk (imp_slice_pack_pcm): measurement m frame-interleaved as int32
+// [out_len][rows_per_meas] at packed + m * meas_stride, column r = row r of the measurement (row 2 q + s: speaker q, side s),
+// every word pcm_word(sample) - the rule rows_to_pcm_kernel writes HRIR.write_wav's files with.
+// A transpose: grid (frame tiles, M), a workgroup owns `tile` frames of one measurement.  Its four waves take the rows in
+// turn and read a row's span coalesced through a buffer resource sized to the span (frames past out_len read nothing),
+// quantise, and leave the words in LDS as [frame][rows | 1]: an odd pitch puts 64 consecutive frames of one row on distinct
+// banks.  The workgroup then writes its [tile][rows] block as one contiguous span, with non-temporal stores (it goes straight
+// to the host).  A measurement with out_len <= 0 (or one the stride cannot hold) is skipped, as slice_pack_f64_kernel skips
+// it.  Dynamic LDS: tile * (rows_per_meas | 1) words.
+__global__ void __launch_bounds__(256) slice_pack_pcm_kernel(const float* __restrict__ rows, long long pitch,
+                                                             const long long* __restrict__ outlen, int rows_per_meas, int tile,
+                                                             int shift, int* __restrict__ packed, long long meas_stride) {
+  extern __shared__ int pcm_tile[];
+  const int R = rows_per_meas, RP = R | 1, m = blockIdx.y;
+  const long long n = outlen[m];
+  const long long f0 = (long long)blockIdx.x * tile;
+  if (n <= 0 || n > pitch || (long long)R * n > meas_stride || f0 >= n) return;
+  const int nf = (int)(n - f0 < tile ? n - f0 : tile);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const float* meas_rows = rows + (long long)m * R * pitch + f0;
+  for (int r = wave; r < R; r += 4) {
+    const __amdgpu_buffer_rsrc_t src = make_rsrc(meas_rows + (long long)r * pitch, (unsigned)nf * 4u);
+    for (int j0 = 0; j0 < nf; j0 += 256) {
+      float x[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) x[u] = bload_f(src, (unsigned)(j0 + 64 * u + lane) * 4u, 0u);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int j = j0 + 64 * u + lane;
+        if (j < nf) pcm_tile[j * RP + r] = pcm_word(x[u], shift);
+      }
+    }
+  }
+  __syncthreads();
+  const int total = nf * R;
+  const __amdgpu_buffer_rsrc_t dst = make_rsrc(packed + (long long)m * meas_stride + f0 * R, (unsigned)total * 4u);
+  const int df = 256 / R, dr = 256 - df * R;
+  int f = (int)threadIdx.x / R, r = (int)threadIdx.x - f * R;      // word k = f * R + r of the block
+  for (int k = threadIdx.x; k < total; k += 256) {
+    __builtin_amdgcn_raw_buffer_store_b32(pcm_tile[f * RP + r], dst, (unsigned)k * 4u, 0u, 2);     // 2: nt
+    f += df;
+    r += dr;
+    if (r >= R) {
+      r -= R;
+      ++f;
+    }
+  }
+}
+
 }  // namespace imp

@@ -135,6 +135,8 @@ SIGNATURES = {
     "imp_xcorr_argmax_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _pi64, _pi64, _i64, _pi64, _pd]),
     "imp_shift_rows_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _pi64, _i64, _vp, _pi64]),
     "imp_slice_pack_f64": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i64]),
+    "imp_slice_pack_pcm": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, _i64]),
+    "imp_pack_pcm_device": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, C.c_int, _vp, _i64]),
     "imp_host_alloc": (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp)]),
     "imp_host_free": (C.c_int, [_vp]),
     "imp_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),
@@ -409,6 +411,12 @@ class Context:
                                                 _ptr_i64(rot), len(rot), int(n_frames), int(bits),
                                                 out.ctypes.data_as(_vp)))
         return out
+
+    def pack_pcm_device(self, d_rows, pitch, d_len, rows_per_meas, M, max_len, bits, d_packed, meas_stride):
+        """imp_pack_pcm_device: M measurements of fp32 device rows (lengths on the device) as frame-interleaved int32 PCM
+        words [len][rows_per_meas], measurement m at d_packed + 4 * m * meas_stride (asynchronous)"""
+        _check(self._lib.imp_pack_pcm_device(self._h, _vp(int(d_rows)), int(pitch), _vp(int(d_len)), int(rows_per_meas), int(M),
+                                             int(max_len), int(bits), _vp(int(d_packed)), int(meas_stride)))
 
     def magnitude_db_sum_device(self, dptr, offs, lens, groups, n_groups, n):
         """[n_groups, ceil(n/2)] dB spectra of the per-group sums of device rows (HRIR.normalize)."""
@@ -804,6 +812,11 @@ class Slice:
     def pack_f64(self, d_out, out_pitch, M, d_packed, meas_stride):
         """the last call's rows as float64, every measurement packed as a [rows][out_len] array (asynchronous)"""
         _check(self._lib.imp_slice_pack_f64(self._h, _vp(int(d_out)), int(out_pitch), int(M), _vp(int(d_packed)), int(meas_stride)))
+
+    def pack_pcm(self, d_out, out_pitch, M, bits, d_packed, meas_stride):
+        """the last call's rows as PCM words (int32), every measurement frame-interleaved as [out_len][rows] (asynchronous)"""
+        _check(self._lib.imp_slice_pack_pcm(self._h, _vp(int(d_out)), int(out_pitch), int(M), int(bits), _vp(int(d_packed)),
+                                            int(meas_stride)))
 
     def close(self):
         if getattr(self, "_h", None):

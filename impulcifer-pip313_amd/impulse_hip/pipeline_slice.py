@@ -130,15 +130,20 @@ def run_slice(estimator, recordings, room_frs=None, target=None, head_ms=1, deca
 
 
 def run_measurement_dirs(estimator, dir_paths, room_frs=None, target=None, head_ms=1, decay=None, peak_target=-0.1,
-                         hp_left=None, hp_right=None, eq_left=None, eq_right=None, align=True, vbass=None):
+                         hp_left=None, hp_right=None, eq_left=None, eq_right=None, align=True, vbass=None, write_brirs=False,
+                         truehd=False, bit_depth=32):
     """The same stage sequence for MANY measurement directories of one layout (a listener measured again, a room measured at
     several seats), each laid out as `open_binaural_measurements` reads it (core/pipeline_stages.py:504-522: `<speaker
     list>.wav` files): the equalisation FIRs are designed once (the curves belong to the job), the recordings are read,
     uploaded, run through the device-resident sequence (imp_slice) and brought back as overlapping stages - one pipeline
     per device of IMPULSE_HIP_DEVICES.  Returns [(HRIR, gain dB)] in the order of dir_paths; every result is what
     run_slice gives for that directory with the same arguments (align defaults to True here: the reference's flow runs
-    the two alignments between crop_heads and crop_tails; vbass as run_slice)."""
-    from .resident_slice import WavMeasurements, run_slice_jobs
+    the two alignments between crop_heads and crop_tails; vbass as run_slice).
+    ``write_brirs``: end as the reference's flow ends (core/pipeline.py:865-876, with ``truehd`` also :878-906): the job
+    runs with output="pcm" (the responses quantised to ``bit_depth`` on the device), each directory receives its hrir.wav,
+    hesuvi.wav [and TrueHD files], and [(BrirFrames, gain dB)] is returned."""
+    from .resident_slice import WavMeasurements, _check_output, run_slice_jobs
+    _check_output("pcm" if write_brirs else "hrir", bit_depth, True)
     job, speakers = WavMeasurements.from_dirs(dir_paths, fs=estimator.fs)
     layout = job.layout(estimator, speakers)
     fs = estimator.fs
@@ -147,5 +152,11 @@ def run_measurement_dirs(estimator, dir_paths, room_frs=None, target=None, head_
         target = FrequencyResponse(name="target", frequency=common.copy(), raw=0)
     firs = {(sp, sd): fir for sp, sd, fir in process_equalization_batch(layout.tasks, room_frs, hp_left, hp_right, eq_left, eq_right,
                                                                         target, common, fs, on_device=True)}
-    return run_slice_jobs(estimator, layout, job, firs, head_ms=head_ms, peak_target=peak_target, decay=decay, align=align,
-                          vbass=vbass)
+    if not write_brirs:
+        return run_slice_jobs(estimator, layout, job, firs, head_ms=head_ms, peak_target=peak_target, decay=decay, align=align,
+                              vbass=vbass)
+    out = run_slice_jobs(estimator, layout, job, firs, head_ms=head_ms, peak_target=peak_target, decay=decay, align=align,
+                         vbass=vbass, output="pcm", bit_depth=bit_depth)
+    for d, (frames, _) in zip(dir_paths, out):
+        frames.write_brirs(d, truehd=truehd)
+    return out

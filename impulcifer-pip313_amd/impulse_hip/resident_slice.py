@@ -18,7 +18,7 @@ import warnings
 import numpy as np
 
 from . import _native
-from .constants import IPSILATERAL_PAIRS, SPEAKER_DELAYS, speaker_side
+from .constants import IPSILATERAL_PAIRS, SPEAKER_DELAYS, speaker_side, track_name
 from .device_rows import DeviceBlock, Row
 from .hrir import HRIR, next_fast_len, split_recording
 from .impulse_response import ImpulseResponse
@@ -364,6 +364,19 @@ class ResidentSlice:
                             for s, sd in enumerate(("left", "right"))}
         return hrir, float(meas["gain_db"][m])
 
+    def collect_pcm(self, words, rows, meas, bit_depth, m=0):
+        """(BrirFrames, gain dB) of measurement m of the last call from its PCM words on the host ([out_len, R] int32, the
+        frame-interleaved layout imp_slice_pack_pcm leaves): the frames are a view of `words`, nothing is copied"""
+        from .brir_frames import BrirFrames
+        R = self.slice.rows
+        self.stats["measurements"] += 1
+        self._warn_sides(rows[m * R:(m + 1) * R])
+        return BrirFrames(self.fs, bit_depth, self.track_names(), words), float(meas["gain_db"][m])
+
+    def track_names(self):
+        """the track name of every row of a measurement (row 2 q + s: speaker q, side s)"""
+        return [track_name(sp, sd) for sp, sd in self.layout.tasks]
+
     def _column(self, recordings, m, q, s):
         if recordings is None:
             return None
@@ -493,12 +506,13 @@ class SliceRunner:
                         rs.upload(d_rec, recs)
                         t1 = time.perf_counter()
                         host = job["to_host"]
-                        block = self._lane_execute(ln, host)
+                        bits = job["bit_depth"] if job["output"] == "pcm" else None
+                        block = self._lane_execute(ln, host, bits)
                         t2 = time.perf_counter()
                         rows, meas = rs.slice.results()
                         t3 = time.perf_counter()
                         if np.any(meas["flags"] & _native.SLICE_KEEP_CAP) and rs.grow_for(rows):
-                            block = self._lane_execute(ln, host)
+                            block = self._lane_execute(ln, host, bits)
                             rows, meas = rs.slice.results()
 
                         def staged(m, recs=recs):
@@ -514,7 +528,15 @@ class SliceRunner:
                             rs.stats["staged"] += 1
                             res = staged(0)
                             t4 = time.perf_counter()
-                            res[0].to_host()
+                            res = _staged_pcm(res, layout, bits) if bits else (res[0].to_host(), res[1])
+                            t5 = time.perf_counter()
+                        elif bits:
+                            # the PCM words over the link into recycled page-locked memory: one linear copy
+                            R, n = rs.slice.rows, int(meas["out_len"][0])
+                            words = _take_words(self.pool, ctx, R * n)
+                            ctx.d2h(words, ln["d_packed"])
+                            t4 = time.perf_counter()
+                            res = rs.collect_pcm(words.reshape(n, R), rows, meas, bits)
                             t5 = time.perf_counter()
                         else:
                             # the packed float64 rows over the link into recycled page-locked memory: one linear copy
@@ -540,9 +562,10 @@ class SliceRunner:
             est._forget_context(ctx)
         ctx.close()
 
-    def _lane_execute(self, ln, host):
-        """one measurement through the lane's slice.  host: the rows stay in a block the lane keeps and are packed as float64
-        for the copy-out (returns None); otherwise a device block of their own is returned, as ResidentSlice.execute_device"""
+    def _lane_execute(self, ln, host, bits=None):
+        """one measurement through the lane's slice.  host: the rows stay in a block the lane keeps and are packed for the
+        copy-out - as float64, or with `bits` as PCM words (the packed block is sized for the float64 rows, which holds either)
+        - and None is returned; otherwise a device block of their own is returned, as ResidentSlice.execute_device"""
         rs, ctx = ln["rs"], ln["ctx"]
         if not host:
             return rs.execute_device(ln["d_rec"], 1)
@@ -555,18 +578,23 @@ class SliceRunner:
             ln["d_packed"] = ctx.malloc(R * cap * 8)
             ln["cap"] = cap
         rs.execute_device(ln["d_rec"], 1, ln["d_out"])
-        rs.slice.pack_f64(ln["d_out"], rs.out_pitch, 1, ln["d_packed"], R * cap)
+        if bits:
+            rs.slice.pack_pcm(ln["d_out"], rs.out_pitch, 1, bits, ln["d_packed"], R * cap)
+        else:
+            rs.slice.pack_f64(ln["d_out"], rs.out_pitch, 1, ln["d_packed"], R * cap)
         return None
 
-    def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None):
+    def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None, output="hrir", bit_depth=32):
         """[(HRIR, gain dB)] in the order of `measurements` ([[frames of file 0, ...], ...]).  firs: {(speaker, side):
         taps}, designed once per job (the curves belong to the job, core/pipeline.py:668-688).  to_host: True = the
         responses as float64 host arrays (as the reference's classes hold them), converted inside the workers;
         False = left on the device.  decay: as ResidentSlice.set_decay; align: as ResidentSlice.set_alignment; vbass: None
-        or the keywords of ResidentSlice.set_virtual_bass."""
+        or the keywords of ResidentSlice.set_virtual_bass.  output="pcm": [(BrirFrames, gain dB)] instead, the responses
+        quantised to `bit_depth` PCM words on the device (brir_frames.BrirFrames writes the files); needs to_host."""
+        _check_output(output, bit_depth, to_host)
         _check_vbass(self.estimator.fs, vbass)
         job = dict(measurements=measurements, firs=firs, to_host=to_host, decay=decay, align=align, vbass=vbass, next=0,
-                   out=[None] * len(measurements))
+                   output=output, bit_depth=int(bit_depth), out=[None] * len(measurements))
         lanes = self.lanes[:max(1, min(len(self.lanes), len(measurements)))]
         with self._run_lock:                               # one job at a time: the lanes' completion markers carry no job identity
             for ln in lanes:
@@ -730,6 +758,7 @@ class SlicePipeline:
                 if job is None:
                     break
                 host = job["to_host"]
+                bits = job["bit_depth"] if job["output"] == "pcm" else None
                 try:
                     rs.set_firs(_firs_for(job["firs"], layout, ctx))
                     rs.set_decay(job["decay"])
@@ -754,7 +783,10 @@ class SlicePipeline:
                             if self.cap != rs.slice.out_len_max:      # grown by a job that left its rows on the device, or a failed re-make
                                 self._rings(held=j)
                             rs.execute_device(self.d_rec[k], 1, self.d_out)
-                            rs.slice.pack_f64(self.d_out, rs.out_pitch, 1, self.d_packed[j], rs.slice.rows * self.cap)
+                            if bits:
+                                rs.slice.pack_pcm(self.d_out, rs.out_pitch, 1, bits, self.d_packed[j], rs.slice.rows * self.cap)
+                            else:
+                                rs.slice.pack_f64(self.d_out, rs.out_pitch, 1, self.d_packed[j], rs.slice.rows * self.cap)
                             return None
 
                         block = once()
@@ -772,11 +804,13 @@ class SlicePipeline:
                             jobs = [((est.fs, np.asarray(fr)), spec[2], None) for fr, spec in zip(recs, layout.files)]
                             res = run_slice(est, jobs, head_ms=self.head_ms, peak_target=self.peak_target, firs=job["firs"],
                                             decay=job["decay"], align=job["align"], vbass=job["vbass"])
-                            if host:
+                            if bits:
+                                res = _staged_pcm(res, layout, bits)
+                            elif host:
                                 res[0].to_host()
                             out = ("result", res)
                         elif host:
-                            out = ("packed", j, rows, meas, recs)
+                            out = ("packed", j, rows, meas, recs, bits)
                             j = None
                         else:
                             out = ("result", rs.collect(block, [recs])[0])
@@ -813,16 +847,22 @@ class SlicePipeline:
                     elif out[0] == "result":
                         job["out"][i] = out[1]
                     else:
-                        _, j, rows, meas, recs = out
+                        _, j, rows, meas, recs, bits = out
                         try:
                             R, n = self.rs.slice.rows, int(meas["out_len"][0])
-                            blk = self.pool.take(ctx, R * n)
-                            flat = np.asarray(blk)[:R * n] if blk is not None else np.empty(R * n)
+                            if bits:
+                                flat = _take_words(self.pool, ctx, R * n)
+                            else:
+                                blk = self.pool.take(ctx, R * n)
+                                flat = np.asarray(blk)[:R * n] if blk is not None else np.empty(R * n)
                             ctx.d2h(flat, self.d_packed[j])
                         finally:
                             self.free_packed.put(j)
                         t2 = time.perf_counter()
-                        job["out"][i] = self.rs.collect_host(flat.reshape(R, n), rows, meas, [recs])
+                        if bits:
+                            job["out"][i] = self.rs.collect_pcm(flat.reshape(n, R), rows, meas, bits)
+                        else:
+                            job["out"][i] = self.rs.collect_host(flat.reshape(R, n), rows, meas, [recs])
                 except BaseException as exc:               # noqa: BLE001
                     self._fail(job, exc)
                 self._add(download_stall=t1 - t0, to_host=t2 - t1, collect=time.perf_counter() - t2)
@@ -831,15 +871,17 @@ class SlicePipeline:
                     job["done"].set()
         ctx.close()
 
-    def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None):
-        """[(HRIR, gain dB)] in the order of `measurements` ([[frames of file 0, ...], ...]); firs, to_host, decay, align and
-        vbass as SliceRunner.run"""
+    def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None, output="hrir", bit_depth=32):
+        """[(HRIR, gain dB)] in the order of `measurements` ([[frames of file 0, ...], ...]); firs, to_host, decay, align,
+        vbass, output and bit_depth as SliceRunner.run"""
+        _check_output(output, bit_depth, to_host)
         _check_vbass(self.estimator.fs, vbass)
         if not len(measurements):
             return []
         import threading
-        job = dict(measurements=measurements, firs=firs, to_host=to_host, decay=decay, align=align, vbass=vbass,
-                   out=[None] * len(measurements), left=len(measurements), error=None, done=threading.Event())
+        job = dict(measurements=measurements, firs=firs, to_host=to_host, decay=decay, align=align, vbass=vbass, output=output,
+                   bit_depth=int(bit_depth), out=[None] * len(measurements), left=len(measurements), error=None,
+                   done=threading.Event())
         with self._submit:                                 # jobs of concurrent callers enter both stage queues in one order
             for q in self.jobs:
                 q.put(job)
@@ -889,18 +931,20 @@ class SliceFleet:
             self.close()
             raise
 
-    def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None):
+    def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None, output="hrir", bit_depth=32):
         from concurrent.futures import ThreadPoolExecutor
         from .sharding import shard_channels
+        _check_output(output, bit_depth, to_host)
         n = len(measurements)
         blocks = [(k,) + shard_channels(n, len(self.pipes), k, keep_pairs=False) for k in range(len(self.pipes))]
         blocks = [(k, lo, hi) for k, lo, hi in blocks if hi > lo]
+        kw = dict(to_host=to_host, decay=decay, align=align, vbass=vbass, output=output, bit_depth=bit_depth)
         if len(blocks) <= 1:
-            return self.pipes[0].run(measurements, firs, to_host=to_host, decay=decay, align=align, vbass=vbass) if n else []
+            return self.pipes[0].run(measurements, firs, **kw) if n else []
 
         def part(item):
             k, lo, hi = item
-            return self.pipes[k].run(measurements[lo:hi], firs, to_host=to_host, decay=decay, align=align, vbass=vbass)
+            return self.pipes[k].run(measurements[lo:hi], firs, **kw)
 
         with ThreadPoolExecutor(max_workers=len(blocks), thread_name_prefix="impulse-fleet") as pool:
             parts = list(pool.map(part, blocks))
@@ -924,17 +968,43 @@ class _Skip(Exception):
 
 
 def run_slice_jobs(estimator, layout, measurements, firs, workers=None, head_ms=1, peak_target=-0.1, decay=None, align=False,
-                   vbass=None):
+                   vbass=None, output="hrir", bit_depth=32):
     """one job through a runner made for it (responses on the host): a three-stage SlicePipeline per device of
-    IMPULSE_HIP_DEVICES (SliceFleet), or with `workers` that many SliceRunner lanes; callers with several jobs keep a runner"""
+    IMPULSE_HIP_DEVICES (SliceFleet), or with `workers` that many SliceRunner lanes; callers with several jobs keep a runner.
+    output="pcm": [(BrirFrames, gain dB)], as SliceRunner.run"""
+    _check_output(output, bit_depth, True)
+    _check_vbass(estimator.fs, vbass)
     if workers is None:
         runner = SliceFleet(estimator, layout, head_ms=head_ms, peak_target=peak_target)
     else:
         runner = SliceRunner(estimator, layout, workers=workers, head_ms=head_ms, peak_target=peak_target)
     try:
-        return runner.run(measurements, firs, to_host=True, decay=decay, align=align, vbass=vbass)
+        return runner.run(measurements, firs, to_host=True, decay=decay, align=align, vbass=vbass, output=output,
+                          bit_depth=bit_depth)
     finally:
         runner.close()
+
+
+def _check_output(output, bit_depth, to_host):
+    """a runner's `output` / `bit_depth` arguments, refused in the caller's thread before any device work"""
+    from .brir_frames import check_bit_depth
+    if output not in ("hrir", "pcm"):
+        raise ValueError(f"output must be 'hrir' or 'pcm', got {output!r}")
+    check_bit_depth(bit_depth)
+    if output == "pcm" and not to_host:
+        raise ValueError("output='pcm' brings PCM words to the host: it needs to_host=True")
+
+
+def _take_words(pool, ctx, words):
+    """int32 [words] in a block of the runner's page-locked pool (ordinary memory beyond its limit)"""
+    blk = pool.take(ctx, -(-words // 2))
+    return np.asarray(blk).view(np.int32)[:words] if blk is not None else np.empty(words, dtype=np.int32)
+
+
+def _staged_pcm(res, layout, bits):
+    """(BrirFrames, gain dB) of a staged-path result: its rows quantised by the host codec in slice column order"""
+    from .brir_frames import BrirFrames
+    return BrirFrames.from_hrir(res[0], layout.tasks, bits), res[1]
 
 
 def vbass_options(fs, crossover_freq=250, head_ms=1.0, hp_freq=15.0, invert_polarity=None):

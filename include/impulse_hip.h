@@ -615,6 +615,21 @@ int imp_slice_results(imp_slice* slice, imp_slice_row_result* rows_out, imp_slic
  * them, core/impulse_response.py:21-27).  meas_stride >= 2 n_pairs * (keep_cap + taps - 1).  The conversion float32 ->
  * float64 is exact; asynchronous on the context's stream, after the call that wrote d_out. */
 int imp_slice_pack_f64(imp_slice* slice, const float* d_out, int64_t out_pitch, int64_t M, double* d_packed, int64_t meas_stride);
+/* The rows of the last call as the PCM words of a WAV data chunk: measurement m frame-interleaved as int32
+ * [out_len(m)][2 n_pairs] at d_packed + m * meas_stride, column r = row r (speaker q, side s at 2 q + s), every word
+ * clip(lrint(x * 2^31), -2^31, 2^31 - 1) >> (32 - bits) - the rule of imp_rows_to_pcm_device, so that one linear copy of
+ * 2 n_pairs * out_len * 4 bytes per measurement brings over what HRIR.write_wav writes, before its track reordering
+ * (resident_slice.SlicePipeline's output="pcm", impulse_hip/brir_frames.py).  bits: 16, 24 or 32 (words sign-extended to
+ * int32).  meas_stride >= 2 n_pairs * (keep_cap + taps - 1); the words of a flagged measurement are not valid.
+ * Asynchronous on the context's stream, after the call that wrote d_out. */
+int imp_slice_pack_pcm(imp_slice* slice, const float* d_out, int64_t out_pitch, int64_t M, int bits, int32_t* d_packed,
+                       int64_t meas_stride);
+/* The same packing for rows that are not a slice's: M measurements of rows_per_meas fp32 rows, row r of measurement m at
+ * d_rows + (m * rows_per_meas + r) * pitch, d_len[m] (device) valid samples, at most max_len <= pitch; measurement m's
+ * words at d_packed + m * meas_stride, meas_stride >= rows_per_meas * max_len.  A measurement with d_len[m] <= 0, or
+ * longer than pitch or than meas_stride holds, is skipped: its words are left as they are (tests/test_resident_pcm.py). */
+int imp_pack_pcm_device(imp_ctx* ctx, const float* d_rows, int64_t pitch, const int64_t* d_len, int64_t rows_per_meas, int64_t M,
+                        int64_t max_len, int bits, int32_t* d_packed, int64_t meas_stride);
 
 /* page-locked host memory (results the link writes straight into: imp_memcpy_d2h to it needs no staging and its pages
  * are mapped once, not per job); imp_host_free takes any pointer imp_host_alloc returned, from any thread */
