@@ -21,12 +21,18 @@ inputs in rotation, so no input line survives in the 256 MiB Infinity Cache betw
 Channels shard across ranks with no data-path collective ("weak": one stream of measurements per GPU); the only
 collective is the one-off RCCL broadcast of the prepared inverse-sweep spectrum.
 
-With N > 1 (or --strong) the line also carries `strong_c5`: BASELINE.json configs[4] (1024 channels x 2^20 samples)
-sharded over the ranks, its IR/s, and the speed-up over rank 0 doing all 1024 channels alone in the same run.
+A plain run does only what `value` needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the
+line, whose other blocks are then null; the peak indices of the timed path's last call are still checked against the
+recordings' known delays.  Everything else is measured with --full:
 
-The JSON line carries `roofline` (HIP-event time of the dominant kernel over the timed steps, priced in ALGORITHMIC
-bytes 8 L per IR, L2<->fabric bytes from rocprofv3 --pmc child runs) and `cpu_baseline` (the NumPy oracle of the same
-chain timed on this box's host cores, rank 0, N = 1).  No torch at N = 1: device memory comes from the library.
+    python bench.py --gpus N --steps K --warmup W --full
+
+With --full the line also carries `deconv_only` (K1 alone, and the other plan kind beside it), `roofline` (HIP-event time of
+the dominant kernel over the timed steps, priced in ALGORITHMIC bytes 8 L per IR, L2<->fabric bytes from rocprofv3 --pmc
+child runs), `cpu_baseline` (the NumPy oracle of the same chain timed on this box's host cores, rank 0, N = 1) with the
+parity checks against it, the `slice` / `slice_resident` blocks (N = 1) and, at N > 1, `strong_c5`: BASELINE.json
+configs[4] (1024 channels x 2^20 samples) sharded over the ranks, its IR/s, and the speed-up over rank 0 doing all 1024
+channels alone in the same run (--strong adds it to any run).  No torch at N = 1: device memory comes from the library.
 """
 import argparse
 import json
@@ -93,6 +99,10 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides `value`, run every other leg: K1 alone and the other plan kind, per-kernel times and the "
+                         "roofline, the CPU baseline and the parity checks against the oracle, the slice blocks, strong_c5 "
+                         "at N > 1 (the --no-* options below trim such a run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--lanes", type=int, default=0,
                     help="chains / K1 launch groups in flight (0: 3 at C2, 2 at C3 - C5); 1 = strictly serial kernels")
@@ -109,8 +119,8 @@ def parse_args(argv=None):
     ap.add_argument("--stage", default="chain", choices=["chain", "deconv", "slice"],
                     help="what `value` times: the deconvolution + FIR chain (the metric) or K1 alone (C4 / C5 always K1)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--strong", action="store_true", help="add the strong_c5 block at N = 1 too")
-    ap.add_argument("--no-strong", action="store_true", help="skip the strong_c5 block at N > 1")
+    ap.add_argument("--strong", action="store_true", help="add the strong_c5 block to any run (without --full, at N = 1)")
+    ap.add_argument("--no-strong", action="store_true", help="skip the strong_c5 block of a --full run at N > 1")
     ap.add_argument("--strong-channels", type=int, default=1024)
     ap.add_argument("--strong-passes", type=int, default=8)
     ap.add_argument("--rehearse-launch", action="store_true",
@@ -1326,43 +1336,47 @@ def main(argv=None):
     peaks_ok = True
     shape = fir_stage_shape(est)
     n_fir, K_fir, head, fade = shape
-    # ---------------------------------------------------------------- K1 alone (secondary; headline for C4 / C5)
+    # ---------------------------------------------------------------- K1 alone (--full; headline for C4 / C5)
     main_paired = k1_paired(args.workload)
-    dec = K1Team(contexts, inv, ring, B, L, pitch, M, group_channels, plan0=lambda c: k1_plan(c, group_channels, main_paired),
-                 paired=main_paired)
     dec_steps = args.steps if stage == "deconv" else max(2, args.steps // 4)
     groups_per_call = -(-B // group_channels)
-    groups_timed = dec_steps * n_blocks * groups_per_call
-    stride = 0 if args.no_events else max(1, min(args.event_stride, groups_timed // 8))
-    dec.set_timing(stride if stage == "deconv" else 0)
-    dec_elapsed = timed_steps(dec, dec_steps, args.warmup if stage == "deconv" else 1)
-    k1_ms, k1_n = dec.timing()
-    dumped = None
-    if stage == "deconv" and args.dump_outputs and rank == 0:
-        # the rows the last K1 launch group of the last timed step wrote (every block holds the same recordings)
-        dumped = dump_outputs(args.dump_outputs, [("deconv_outputs", dec.outputs()[(dec.n - 1) % len(dec.lanes)])])
-    # the same kernels with nothing else on the chip (launch groups strictly serial: one stream), outside the timed
-    # region: under overlap a kernel's event-to-event time includes the share of the chip it cedes to the other groups
-    barrier(dec)
-    dec.set_timing(1)
-    for p in ring.ptrs[:max(4, min(40, n_blocks))]:
-        dec.call(p, lane=0)
-    dec.sync()
-    iso_ms, iso_n = dec.timing(lanes=[0])
-    dec.set_timing(0)
-    for i, p in enumerate(ring.ptrs[:len(contexts)]):          # every lane's output written by the overlapped form again
-        dec.call(p, lane=i)
-    dec.sync()
-    ys = dec.outputs()
-    for y in ys:
-        peaks_ok &= all(int(np.argmax(np.abs(y[c]))) == M // 2 + delays[c] for c in range(B))
-    y_k1 = ys[-1]
-    nfft, plan_ws, skew = dec.plan.nfft, dec.plan.ws_channels * len(contexts), dec.skew
-    dec.release()
-    dec_rate_rank = irs_per_step_rank * dec_steps / dec_elapsed
+    dumped = dec_rate_rank = None
+    if stage == "deconv" or args.full:
+        dec = K1Team(contexts, inv, ring, B, L, pitch, M, group_channels, plan0=lambda c: k1_plan(c, group_channels, main_paired),
+                     paired=main_paired)
+        groups_timed = dec_steps * n_blocks * groups_per_call
+        stride = 0 if args.no_events else max(1, min(args.event_stride, groups_timed // 8))
+        dec.set_timing(stride if stage == "deconv" else 0)
+        dec_elapsed = timed_steps(dec, dec_steps, args.warmup if stage == "deconv" else 1)
+        k1_ms, k1_n = dec.timing()
+        if stage == "deconv" and args.dump_outputs and rank == 0:
+            # the rows the last K1 launch group of the last timed step wrote (every block holds the same recordings)
+            dumped = dump_outputs(args.dump_outputs, [("deconv_outputs", dec.outputs()[(dec.n - 1) % len(dec.lanes)])])
+        if args.full:
+            # the same kernels with nothing else on the chip (launch groups strictly serial: one stream), outside the timed
+            # region: under overlap a kernel's event-to-event time includes the share of the chip it cedes to the other groups
+            barrier(dec)
+            dec.set_timing(1)
+            for p in ring.ptrs[:max(4, min(40, n_blocks))]:
+                dec.call(p, lane=0)
+            dec.sync()
+            iso_ms, iso_n = dec.timing(lanes=[0])
+            dec.set_timing(0)
+            for i, p in enumerate(ring.ptrs[:len(contexts)]):      # every lane's output written by the overlapped form again
+                dec.call(p, lane=i)
+            dec.sync()
+            ys = dec.outputs()
+        else:
+            ys = [dec.outputs()[(dec.n - 1) % len(dec.lanes)]]     # the lane of the last timed call
+        for y in ys:
+            peaks_ok &= all(int(np.argmax(np.abs(y[c]))) == M // 2 + delays[c] for c in range(B))
+        y_k1 = ys[-1]
+        nfft, plan_ws, skew = dec.plan.nfft, dec.plan.ws_channels * len(contexts), dec.skew
+        dec.release()
+        dec_rate_rank = irs_per_step_rank * dec_steps / dec_elapsed
     # the other plan kind on the same planar rows (pair mode = two channels per complex transform, where the lengths allow it)
     pair_block, y_pair = None, None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             from impulse_hip._native import plan_geometry_paired
             if main_paired or plan_geometry_paired(M, L, "same") is not None:
@@ -1406,6 +1420,9 @@ def main(argv=None):
             dumped = dump_outputs(args.dump_outputs, [("chain_outputs", y_last), ("chain_peak_indices", pk_last)])
         firs = team.firs
         peaks_ok &= all(abs(int(pk_chain[c]) - (M // 2 + delays[c])) <= 8 for c in range(B))   # exact check: against the oracle below
+        if dec_rate_rank is None:                             # no K1-alone leg: the config names the chain's K1 plans
+            plan1 = team.lanes[0]["plan1"]
+            nfft, plan_ws = plan1.nfft, plan1.ws_channels * len(team.lanes)
     if dist is not None:                      # rank 0 reports the verdict of every rank
         flag = torch.tensor([1 if peaks_ok else 0], dtype=torch.int32, device=comm_device)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
@@ -1415,7 +1432,7 @@ def main(argv=None):
     ring.release()
 
     strong_c5 = None
-    if (world > 1 and not args.no_strong) or args.strong:
+    if (args.full and world > 1 and not args.no_strong) or args.strong:
         strong_c5, s_ok = strong_block(args, torch, dist, comm_device, device, ctx, rank, world, backend)
         peaks_ok &= s_ok
 
@@ -1431,7 +1448,7 @@ def main(argv=None):
         steps_timed = args.steps if stage == "chain" else dec_steps
         elapsed = chain_elapsed if stage == "chain" else dec_elapsed
         value = irs_per_step * steps_timed / elapsed
-        dec_value = dec_rate_rank * world
+        dec_value = None if dec_rate_rank is None else dec_rate_rank * world
         # channels per K1 launch group: of the leg whose HIP events time the kernels (the chain deconvolves a whole call as ONE
         # group, K1 alone runs groups of `group_channels`), of the serial isolated calls (K1 alone), of the --pmc children
         timed_group = B if stage == "chain" else group_channels
@@ -1443,7 +1460,7 @@ def main(argv=None):
         # per-kernel times over the TIMED region: from the chains' K1 plans when the chain is what is timed
         t_ms, t_n = (chain_k1 if stage == "chain" else (np.asarray(k1_ms), k1_n))
         roof = None
-        if t_n > 0:
+        if args.full and t_n > 0:
             avg_ms = [float(m) / t_n for m in t_ms]
             dom = int(np.argmax(avg_ms))
             achieved = alg_k1_launch / (avg_ms[dom] * 1e-3) / 1e9
@@ -1509,7 +1526,7 @@ def main(argv=None):
                          "see traffic_note) / this run's time per call.  Infinity-Cache hits are counted, so this is a FABRIC "
                          "rate, not achieved HBM bandwidth; it is not compared with the HBM peak")
         cpu, parity = None, dict(peak_indices_exact=bool(peaks_ok))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             with_fir = stage == "chain"
             cpu, outs = cpu_baseline(est, rec, L, firs, shape, with_fir)
             errs, errs_full, errs_full_pair, chain_errs = [], [], [], []
@@ -1556,12 +1573,12 @@ def main(argv=None):
             peaks_ok &= max(errs_full) <= column_gate
             parity["peak_indices_exact"] = bool(peaks_ok)
         whole_slice = slice_res = None
-        if world == 1 and args.workload == "c2" and not args.no_cpu_baseline and not args.no_slice:
+        if args.full and world == 1 and args.workload == "c2" and not args.no_cpu_baseline and not args.no_slice:
             try:
                 whole_slice = slice_rate(est, rec[:B_meas], L)
             except Exception as exc:                          # noqa: BLE001 - secondary figure only
                 whole_slice = dict(error=repr(exc))
-        if world == 1 and args.workload in ("c2", "c3") and not args.no_slice:
+        if args.full and world == 1 and args.workload in ("c2", "c3") and not args.no_slice:
             try:
                 slice_res = slice_resident_block(est, rec[:B_meas], L, args.workload, no_pmc=args.no_pmc)
                 peaks_ok &= bool(slice_res["bit_identical_to_staged_path"])
@@ -1571,7 +1588,7 @@ def main(argv=None):
             "metric": METRIC, "value": value, "unit": "IR/s", "n_gpus": world, "steps": steps_timed,
             "warmup": args.warmup, "ms_per_step": elapsed / steps_timed * 1e3,
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic", "timed_region_s": elapsed, "irs_per_step": irs_per_step,
+            "data": "synthetic", "timed_region_s": elapsed, "irs_per_step": irs_per_step, "full": bool(args.full),
             "ranks_seen": dist.get_world_size() if dist is not None else 1, "rccl_ranks_seen": RCCL_RANKS_SEEN,
             "config": {"workload": desc,
                        "stage": ("sweep deconvolution + FIR as the metric names it: K1 deconvolution ('same' crop) -> K3 first peak -> "
@@ -1604,7 +1621,7 @@ def main(argv=None):
                                        "cropped stores fall on cache lines",
                                 plan="pair" if main_paired else "mono",
                                 note="K1 alone over the same resident inputs, algorithmic bytes 8 L per IR",
-                                other_plan=pair_block),
+                                other_plan=pair_block) if dec_value is not None else None,
             "slice": whole_slice, "slice_resident": slice_res, "strong_c5": strong_c5,
         }
         if dumped is not None:

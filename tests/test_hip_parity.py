@@ -1509,7 +1509,7 @@ def _bench_line(res):
 
 
 def test_bench_contract_line(gpu_ctx):
-    """bench.py prints exactly one JSON line on stdout with the contract's keys, BASELINE.json's metric, a
+    """bench.py --full prints exactly one JSON line on stdout with the contract's keys, BASELINE.json's metric, a
     roofline block and (at N = 1) a cpu_baseline block; everything else goes to stderr.  `value` times the metric's own
     wording - the deconvolution + FIR chain - and K1 alone is given beside it (`deconv_only`).  A step is one pass over all
     resident measurements (10 240 IRs), so the contract's 20 steps time about half a second."""
@@ -1517,9 +1517,10 @@ def test_bench_contract_line(gpu_ctx):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "2"],
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "2", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=root)
     d = _bench_line(res)
+    assert d["full"] is True
     base = json.load(open(os.path.join(root, "BASELINE.json")))
     assert d["metric"] == base["metric"] and d["unit"] == "IR/s"
     for key in ("value", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -1565,9 +1566,32 @@ def test_bench_contract_line(gpu_ctx):
     assert isinstance(cfg["environment_switches"], dict)
 
 
+def test_bench_plain_line(gpu_ctx):
+    """Without --full a run only sets up, warms up, times the chain and prints the line: the same headline keys, meaning
+    what they mean in a --full run, every other block null, and the peak indices of the timed chain checked against the
+    recordings' known delays."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2"],
+                         capture_output=True, text=True, timeout=300, cwd=root)
+    d = _bench_line(res)
+    base = json.load(open(os.path.join(root, "BASELINE.json")))
+    assert d["metric"] == base["metric"] and d["unit"] == "IR/s" and d["dtype"] == "f32" and d["full"] is False
+    assert (d["n_gpus"], d["steps"], d["warmup"], d["scaling"], d["higher_is_better"]) == (1, 10, 2, "weak", True)
+    assert abs(d["timed_region_s"] * 1e3 - d["ms_per_step"] * 10) < 1e-6
+    assert abs(d["value"] - d["irs_per_step"] * d["steps"] / d["timed_region_s"]) <= 1e-6 * d["value"]
+    cfg = d["config"]
+    assert d["irs_per_step"] == 10240 and "FIR" in cfg["stage"] and cfg["fir_taps"] == 9600 and cfg["nfft"] > 0
+    assert d["parity"] == {"peak_indices_exact": True}
+    for key in ("roofline", "cpu_baseline", "deconv_only", "slice", "slice_resident", "strong_c5"):
+        assert d[key] is None, key
+
+
 def test_bench_two_ranks_started_plainly(gpu_ctx):
     """`python bench.py --gpus 2 ...` invoked PLAINLY (no torchrun, no WORLD_SIZE) starts its own two ranks as a child
-    before touching the GPU, and rank 0 prints one line with the weak C2 figure and the strong_c5 block.  On this
+    before touching the GPU, and rank 0 prints one line with the weak C2 figure and (--full) the strong_c5 block.  On this
     one-GPU box the ranks are folded onto device 0 and rendezvous over gloo (IMPULSE_BENCH_BACKEND=gloo)."""
     import subprocess
     import sys
@@ -1575,7 +1599,7 @@ def test_bench_two_ranks_started_plainly(gpu_ctx):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["IMPULSE_BENCH_BACKEND"] = "gloo"
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-                          "--blocks", "24", "--strong-channels", "128", "--strong-passes", "2"],
+                          "--blocks", "24", "--strong-channels", "128", "--strong-passes", "2", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=root, env=env)
     d = _bench_line(res)
     assert (d["n_gpus"], d["ranks_seen"], d["scaling"]) == (2, 2, "weak") and d["value"] > 0

@@ -375,6 +375,13 @@ def test_bench_rank_mismatch_is_an_error():
     assert res.returncode != 0 and "WORLD_SIZE=3" in res.stderr
 
 
+def test_bench_full_is_opt_in():
+    """A plain run measures `value` alone; the other legs (K1 alone, roofline, CPU baseline and parity, slices) need --full."""
+    import bench
+    assert bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"]).full is False
+    assert bench.parse_args(["--gpus", "1", "--full"]).full is True
+
+
 def test_product_from_wav_branches(golden, tmp_path):
     """ImpulseResponseEstimator.from_wav (reference core/impulse_response_estimator.py:234-262), all three branches,
     against a reference run: off-grid length -> the file's samples become the sweep; on-grid but > 1e-4 away -> same,

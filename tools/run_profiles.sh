@@ -10,10 +10,10 @@ OUT=$R/gpurun_out/prof_round
 TAG=${ROUND_TAG:-r04}
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pmc --no-slice > $OUT/bench_trace.json 2> $OUT/bench_trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-pmc --no-slice > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 echo "trace done"
 # the same command with one chain: every kernel owns the chip while it runs (clean per-kernel roofline)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_serial -o bench -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pmc --no-slice --lanes 1 --blocks 48 > $OUT/bench_trace_serial.json 2> $OUT/bench_trace_serial.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_serial -o bench -- python3 $R/bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-pmc --no-slice --lanes 1 --blocks 48 > $OUT/bench_trace_serial.json 2> $OUT/bench_trace_serial.err
 echo "serial trace done"
 # the resident slice: one stream (serial kernels) and three
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_slice_serial -o s -- python3 $R/tools/slice_resident_rate.py c2 1 8 20 3 > $OUT/slice_rate_serial.txt 2>&1
@@ -27,12 +27,12 @@ for W in c2 c3 c5; do
 done
 echo "pmc done"
 cd $R
-python3 bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+python3 bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err
 echo "c2 done"
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_c2_steps20.json 2> $OUT/bench_c2_steps20.err
-python3 bench.py --workload c3 > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_c2_steps20.json 2> $OUT/bench_c2_steps20.err
+python3 bench.py --workload c3 --full > $OUT/bench_c3.json 2> $OUT/bench_c3.err
 echo "c3 done"
-python3 bench.py --workload c5 --steps 8 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+python3 bench.py --workload c5 --steps 8 --full > $OUT/bench_c5.json 2> $OUT/bench_c5.err
 echo "c5 done"
 python3 tools/slice_e2e_rate.py 0 48 > $OUT/slice_e2e.txt 2>&1
 python3 tools/slice_e2e_rate.py 3 48 >> $OUT/slice_e2e.txt 2>&1
