@@ -142,8 +142,9 @@ def run_measurement_dirs(estimator, dir_paths, room_frs=None, target=None, head_
     ``write_brirs``: end as the reference's flow ends (core/pipeline.py:865-876, with ``truehd`` also :878-906): the job
     runs with output="pcm" (the responses quantised to ``bit_depth`` on the device), each directory receives its hrir.wav,
     hesuvi.wav [and TrueHD files], and [(BrirFrames, gain dB)] is returned."""
-    from .resident_slice import WavMeasurements, _check_output, run_slice_jobs
-    _check_output("pcm" if write_brirs else "hrir", bit_depth, True)
+    from .resident_slice import WavMeasurements, _slice_job, run_slice_jobs
+    # the runner's arguments refused before any file is read
+    _slice_job(estimator.fs, [], None, vbass=vbass, output="pcm" if write_brirs else "hrir", bit_depth=bit_depth)
     job, speakers = WavMeasurements.from_dirs(dir_paths, fs=estimator.fs)
     layout = job.layout(estimator, speakers)
     fs = estimator.fs

@@ -326,19 +326,18 @@ class ResidentSlice:
 
     def collect(self, block, recordings=None, staged=None):
         """[(HRIR, gain dB)] of the last call.  Measurements the device flagged are replaced by staged(m) (the staged
-        path of measurement m); without `staged` a flagged measurement raises."""
+        path of measurement m, through ResidentSlice.staged); without `staged` a flagged measurement raises."""
         rows, meas = self.slice.results()
         R = self.slice.rows
         out = []
         for m in range(len(meas)):
-            self.stats["measurements"] += 1
             fl = int(meas["flags"][m])
             if fl & _native.SLICE_REDO:
-                self.stats["staged"] += 1
                 if staged is None:
                     raise _native.NativeError(-3, f"measurement {m}: the device left a decision to the staged path (flags {fl})")
                 out.append(staged(m))
                 continue
+            self.stats["measurements"] += 1
             self._warn_sides(rows[m * R:(m + 1) * R])
             hrir = HRIR(self.estimator)
             n = int(meas["out_len"][m])
@@ -402,11 +401,9 @@ class ResidentSlice:
         """measurements: [[frames of file 0, frames of file 1, ...], ...] in host memory.  Returns [(HRIR, gain dB)]:
         uploads, runs the resident sequence in calls of up to max_measurements, replaces flagged measurements by the
         staged path."""
-        from .pipeline_slice import run_slice
         if self.firs is None:
             raise ValueError("set_firs first")
         results = []
-        firs = None
         for m0 in range(0, len(measurements), self.max_measurements):
             batch = measurements[m0:m0 + self.max_measurements]
             M = len(batch)
@@ -414,20 +411,108 @@ class ResidentSlice:
             try:
                 for m, recs in enumerate(batch):
                     self.ctx.h2d(d_rec + m * self.layout.samples * self.layout.dtype.itemsize, self.layout.pack(recs))
-                block = self.execute_device(d_rec, M)
-                rows, meas = self.slice.results()
-                if np.any(meas["flags"] & _native.SLICE_KEEP_CAP) and self.grow_for(rows):
-                    block = self.execute_device(d_rec, M)      # once more, with room for the longest response
+                block, _, _ = self.execute(d_rec, M)
             finally:
                 self.ctx.free(d_rec)                       # ordered on the stream
-
-            def staged(m, batch=batch):
-                jobs = [((self.fs, np.asarray(fr)), spec[2], None) for fr, spec in zip(batch[m], self.layout.files)]
-                return run_slice(self.estimator, jobs, head_ms=self.head_ms, peak_target=self.peak_target, firs=self.firs_by_task(),
-                                 decay=self.decay, align=self.align, vbass=self.vbass)
-
-            results.extend(self.collect(block, batch, staged))
+            results.extend(self.collect(block, batch, lambda m: self.staged(batch[m], self.firs_by_task())))
         return results
+
+    # ---- one measurement of a runner's job: the job runners (SliceRunner, SlicePipeline) only schedule these
+    def apply(self, job):
+        """a runner job's options (_slice_job) on the slice: FIRs (those a design left on another device as host taps),
+        decay, alignments, virtual bass"""
+        self.set_firs(_firs_for(job["firs"], self.layout, self.ctx))
+        self.set_decay(job["decay"])
+        self.set_alignment(job["align"])
+        if job["vbass"] is None:
+            self.set_virtual_bass(None)
+        else:
+            self.set_virtual_bass(**job["vbass"])
+
+    def execute(self, d_rec, M, buffers=None, bits=None, times=None):
+        """(device block or None, rows, meas) of M measurements at d_rec (layout.samples apart); a call that flagged
+        IMP_SLICE_KEEP_CAP is repeated once, on a slice grown for its responses.  buffers: None = the rows in a device block
+        of their own (returned); otherwise a function giving (d_out, d_packed) for the slice's present capacity - the caller
+        re-sizes its own buffers there when the capacity has changed - and the rows are packed into d_packed on the device,
+        as float64 or with `bits` as PCM words (the packed block is sized for the float64 rows, which holds either).
+        times: a dict whose 'launch' and 'wait' the first call's seconds are added to."""
+        def once():
+            if buffers is None:
+                return self.execute_device(d_rec, M)
+            d_out, d_packed = buffers()
+            self.execute_device(d_rec, M, d_out)
+            stride = self.slice.rows * self.slice.out_len_max
+            if bits:
+                self.slice.pack_pcm(d_out, self.out_pitch, M, bits, d_packed, stride)
+            else:
+                self.slice.pack_f64(d_out, self.out_pitch, M, d_packed, stride)
+            return None
+
+        t0 = time.perf_counter()
+        block = once()
+        t1 = time.perf_counter()
+        rows, meas = self.slice.results()
+        if times is not None:
+            times["launch"] += t1 - t0
+            times["wait"] += time.perf_counter() - t1
+        if np.any(meas["flags"] & _native.SLICE_KEEP_CAP) and self.grow_for(rows):
+            block = once()                                 # once more, with room for the longest response
+            rows, meas = self.slice.results()
+        return block, rows, meas
+
+    def measure(self, d_rec, recordings, job, buffers, times=None):
+        """one measurement of a runner's job (its recordings uploaded to d_rec, the job applied): (result, None) when it is
+        complete - the staged path's for a measurement the device flagged, device rows with to_host=False - or
+        (None, (rows, meas)) when its rows wait packed in buffers()'s d_packed for copy_out"""
+        block, rows, meas = self.execute(d_rec, 1, buffers if job["to_host"] else None, job["bits"], times)
+        if int(meas["flags"][0]) & _native.SLICE_REDO:
+            return self.staged(recordings, job["firs"], job["to_host"], job["bits"]), None
+        if not job["to_host"]:
+            return self.collect(block, [recordings])[0], None
+        return None, (rows, meas)
+
+    def staged(self, recordings, firs, to_host=False, bits=None):
+        """(HRIR, gain dB) of one measurement through the staged path (`run_slice`) with the slice's options and `firs`: a
+        measurement the device flagged.  to_host: the responses as float64 host arrays; bits: (BrirFrames, gain dB), the rows
+        quantised by the host codec in slice column order."""
+        from .brir_frames import BrirFrames
+        from .pipeline_slice import run_slice
+        self.stats["measurements"] += 1
+        self.stats["staged"] += 1
+        jobs = [((self.fs, np.asarray(fr)), spec[2], None) for fr, spec in zip(recordings, self.layout.files)]
+        hrir, gain = run_slice(self.estimator, jobs, head_ms=self.head_ms, peak_target=self.peak_target, firs=firs,
+                               decay=self.decay, align=self.align, vbass=self.vbass)
+        if bits:
+            return BrirFrames.from_hrir(hrir, self.layout.tasks, bits), gain
+        return (hrir.to_host() if to_host else hrir), gain
+
+    def copy_out(self, pool, ctx, d_packed, rows, meas, recordings=None, bits=None, release=None, times=None):
+        """(HRIR or BrirFrames, gain dB) of the last call's measurement from its rows packed at d_packed (execute with
+        buffers): one linear copy on ctx's stream into recycled page-locked memory (pool; ordinary memory beyond its limit),
+        the results views of it.  release(): called as soon as d_packed has been read, also when the copy fails.  times: a
+        dict whose 'to_host' and 'collect' the seconds are added to."""
+        R, n = self.slice.rows, int(meas["out_len"][0])
+        t0 = time.perf_counter()
+        try:
+            if bits:                                       # int32 words, frame-interleaved [out_len][R]
+                blk = pool.take(ctx, -(-R * n // 2))
+                flat = np.asarray(blk).view(np.int32)[:R * n] if blk is not None else np.empty(R * n, dtype=np.int32)
+            else:                                          # float64 rows [R][out_len]
+                blk = pool.take(ctx, R * n)
+                flat = np.asarray(blk)[:R * n] if blk is not None else np.empty(R * n)
+            ctx.d2h(flat, d_packed)
+        finally:
+            if release is not None:
+                release()
+        t1 = time.perf_counter()
+        if bits:
+            res = self.collect_pcm(flat.reshape(n, R), rows, meas, bits)
+        else:
+            res = self.collect_host(flat.reshape(R, n), rows, meas, recordings)
+        if times is not None:
+            times["to_host"] += t1 - t0
+            times["collect"] += time.perf_counter() - t1
+        return res
 
     def upload(self, d_rec, recordings, ctx=None):
         """the files of one measurement to their places in a device block (no host-side packing: every file goes up as it
@@ -472,117 +557,66 @@ class SliceRunner:
 
     def _worker(self, ln):
         """a lane's thread: makes its context and slice, then serves jobs until it is told to stop"""
-        from .pipeline_slice import run_slice
         est, layout = self.estimator, self.layout
         try:
             ctx = _native.Context(_native.default_device())
             with _native.using_context(ctx):
                 rs = ResidentSlice(est, layout, max_measurements=1, head_ms=self.head_ms, peak_target=self.peak_target)
             d_rec = ctx.malloc(layout.samples * layout.dtype.itemsize)
-            ln.update(ctx=ctx, rs=rs, d_rec=d_rec)
+            ln.update(ctx=ctx, rs=rs, d_rec=d_rec, d_out=0, d_packed=0, cap=None)
         except BaseException as exc:                       # noqa: BLE001 - reported to the constructor
             ln["error"] = exc
             ln["ready"].set()
             return
         ln["ready"].set()
+
+        def buffers():
+            """the lane's row block and packed block for the slice's present capacity"""
+            R, cap = rs.slice.rows, rs.slice.out_len_max
+            if ln["cap"] != cap:                           # first measurement, or the slice was re-made for longer responses
+                for k in ("d_out", "d_packed"):
+                    if ln[k]:
+                        ctx.free(ln[k])
+                        ln[k] = 0
+                ln["d_out"] = ctx.malloc(R * rs.out_pitch * 4)
+                ln["d_packed"] = ctx.malloc(R * cap * 8)
+                ln["cap"] = cap
+            return ln["d_out"], ln["d_packed"]
+
         with _native.using_context(ctx):
             while True:
                 job = ln["todo"].get()
                 if job is None:
                     break
                 try:
-                    rs.set_firs(job["firs"])
-                    rs.set_decay(job["decay"])
-                    rs.set_alignment(job["align"])
-                    _set_vbass(rs, job["vbass"])
+                    rs.apply(job)
                     while True:
                         with self._lock:
                             i = job["next"]
                             job["next"] += 1
-                        if i >= len(job["measurements"]):
+                        if i >= job["n"]:
                             break
                         recs = job["measurements"][i]
+                        t = dict(upload=0.0, launch=0.0, wait=0.0, to_host=0.0, collect=0.0, measurements=1)
                         t0 = time.perf_counter()
                         rs.upload(d_rec, recs)
-                        t1 = time.perf_counter()
-                        host = job["to_host"]
-                        bits = job["bit_depth"] if job["output"] == "pcm" else None
-                        block = self._lane_execute(ln, host, bits)
-                        t2 = time.perf_counter()
-                        rows, meas = rs.slice.results()
-                        t3 = time.perf_counter()
-                        if np.any(meas["flags"] & _native.SLICE_KEEP_CAP) and rs.grow_for(rows):
-                            block = self._lane_execute(ln, host, bits)
-                            rows, meas = rs.slice.results()
-
-                        def staged(m, recs=recs):
-                            jobs = [((est.fs, np.asarray(fr)), spec[2], None) for fr, spec in zip(recs, layout.files)]
-                            return run_slice(est, jobs, head_ms=self.head_ms, peak_target=self.peak_target, firs=job["firs"],
-                                             decay=job["decay"], align=job["align"], vbass=job["vbass"])
-
-                        if not host:
-                            res = rs.collect(block, [recs], staged)[0]
-                            t4 = t5 = time.perf_counter()
-                        elif int(meas["flags"][0]) & _native.SLICE_REDO:
-                            rs.stats["measurements"] += 1
-                            rs.stats["staged"] += 1
-                            res = staged(0)
-                            t4 = time.perf_counter()
-                            res = _staged_pcm(res, layout, bits) if bits else (res[0].to_host(), res[1])
-                            t5 = time.perf_counter()
-                        elif bits:
-                            # the PCM words over the link into recycled page-locked memory: one linear copy
-                            R, n = rs.slice.rows, int(meas["out_len"][0])
-                            words = _take_words(self.pool, ctx, R * n)
-                            ctx.d2h(words, ln["d_packed"])
-                            t4 = time.perf_counter()
-                            res = rs.collect_pcm(words.reshape(n, R), rows, meas, bits)
-                            t5 = time.perf_counter()
-                        else:
-                            # the packed float64 rows over the link into recycled page-locked memory: one linear copy
-                            R, n = rs.slice.rows, int(meas["out_len"][0])
-                            blk = self.pool.take(ctx, R * n)
-                            flat = np.asarray(blk)[:R * n] if blk is not None else np.empty(R * n)
-                            ctx.d2h(flat, ln["d_packed"])
-                            t4 = time.perf_counter()
-                            res = rs.collect_host(flat.reshape(R, n), rows, meas, [recs])
-                            t5 = time.perf_counter()
+                        t["upload"] = time.perf_counter() - t0
+                        res, packed = rs.measure(d_rec, recs, job, buffers, t)
+                        if packed is not None:
+                            res = rs.copy_out(self.pool, ctx, ln["d_packed"], *packed, [recs], job["bits"], times=t)
                         job["out"][i] = res
-                        for k, dt in (("upload", t1 - t0), ("launch", t2 - t1), ("wait", t3 - t2), ("to_host", t4 - t3),
-                                      ("collect", t5 - t4), ("measurements", 1)):
+                        for k, dt in t.items():
                             ln["times"][k] = ln["times"].get(k, 0.0) + dt
                     ln["done"].put(None)
                 except BaseException as exc:               # noqa: BLE001 - re-raised in the caller's thread
                     ln["done"].put(exc)
             ctx.free(d_rec)
             for k in ("d_out", "d_packed"):
-                if ln.get(k):
+                if ln[k]:
                     ctx.free(ln[k])
             rs.close()
             est._forget_context(ctx)
         ctx.close()
-
-    def _lane_execute(self, ln, host, bits=None):
-        """one measurement through the lane's slice.  host: the rows stay in a block the lane keeps and are packed for the
-        copy-out - as float64, or with `bits` as PCM words (the packed block is sized for the float64 rows, which holds either)
-        - and None is returned; otherwise a device block of their own is returned, as ResidentSlice.execute_device"""
-        rs, ctx = ln["rs"], ln["ctx"]
-        if not host:
-            return rs.execute_device(ln["d_rec"], 1)
-        R, cap = rs.slice.rows, rs.slice.out_len_max
-        if ln.get("cap") != cap:                           # first measurement, or the slice was re-made for longer responses
-            for k in ("d_out", "d_packed"):
-                if ln.get(k):
-                    ctx.free(ln[k])
-            ln["d_out"] = ctx.malloc(R * rs.out_pitch * 4)
-            ln["d_packed"] = ctx.malloc(R * cap * 8)
-            ln["cap"] = cap
-        rs.execute_device(ln["d_rec"], 1, ln["d_out"])
-        if bits:
-            rs.slice.pack_pcm(ln["d_out"], rs.out_pitch, 1, bits, ln["d_packed"], R * cap)
-        else:
-            rs.slice.pack_f64(ln["d_out"], rs.out_pitch, 1, ln["d_packed"], R * cap)
-        return None
 
     def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None, output="hrir", bit_depth=32):
         """[(HRIR, gain dB)] in the order of `measurements` ([[frames of file 0, ...], ...]).  firs: {(speaker, side):
@@ -591,11 +625,8 @@ class SliceRunner:
         False = left on the device.  decay: as ResidentSlice.set_decay; align: as ResidentSlice.set_alignment; vbass: None
         or the keywords of ResidentSlice.set_virtual_bass.  output="pcm": [(BrirFrames, gain dB)] instead, the responses
         quantised to `bit_depth` PCM words on the device (brir_frames.BrirFrames writes the files); needs to_host."""
-        _check_output(output, bit_depth, to_host)
-        _check_vbass(self.estimator.fs, vbass)
-        job = dict(measurements=measurements, firs=firs, to_host=to_host, decay=decay, align=align, vbass=vbass, next=0,
-                   output=output, bit_depth=int(bit_depth), out=[None] * len(measurements))
-        lanes = self.lanes[:max(1, min(len(self.lanes), len(measurements)))]
+        job = _slice_job(self.estimator.fs, measurements, firs, to_host, decay, align, vbass, output, bit_depth)
+        lanes = self.lanes[:max(1, min(len(self.lanes), job["n"]))]
         with self._run_lock:                               # one job at a time: the lanes' completion markers carry no job identity
             for ln in lanes:
                 ln["todo"].put(job)
@@ -649,6 +680,7 @@ class SlicePipeline:
         self._tlock = threading.Lock()
         self.state = dict(error=None, ready=threading.Event())
         self.ctxs = [None, None, None]
+        self.d_rec, self.d_out, self.d_packed, self.cap = [], 0, [], None
         self.threads = [threading.Thread(target=fn, name=f"impulse-slice-{name}", daemon=True)
                         for fn, name in ((self._compute, "compute"), (self._upload, "upload"), (self._download, "download"))]
         self.threads[0].start()                            # makes the slice and the rings, then the others start
@@ -691,6 +723,9 @@ class SlicePipeline:
         if job["error"] is None:
             job["error"] = exc
 
+    # Every index of a job passes through all three stages, whatever a stage raised while serving it: the error fails the
+    # job (run() raises the first one), and the stages go on to the next job.
+
     # ---- stage 1: the link, upward
     def _upload(self):
         ctx = self.ctxs[1] = _native.Context(self.device)
@@ -699,19 +734,20 @@ class SlicePipeline:
                 job = self.jobs[1].get()
                 if job is None:
                     break
-                for i, recs in enumerate(job["measurements"]):
-                    t0 = time.perf_counter()
-                    k = self.free_rec.get()
-                    t1 = time.perf_counter()
-                    ok = job["error"] is None
-                    if ok:
+                for i in range(job["n"]):
+                    t0 = t1 = time.perf_counter()
+                    k = recs = None                        # (a failed job's measurements are neither read nor uploaded)
+                    if job["error"] is None:
                         try:
+                            recs = job["measurements"][i]      # (a WAV file is read here, before the wait for a buffer)
+                            t0 = time.perf_counter()
+                            k = self.free_rec.get()
+                            t1 = time.perf_counter()
                             self.rs.upload(self.d_rec[k], recs, ctx)
                         except BaseException as exc:       # noqa: BLE001 - re-raised by run()
                             self._fail(job, exc)
-                            ok = False
                     self._add(upload_stall=t1 - t0, upload=time.perf_counter() - t1)
-                    self.uploaded.put((i, k, recs, ok))
+                    self.uploaded.put((i, k, recs))
         ctx.close()
 
     # ---- stage 2: the stage sequence
@@ -723,20 +759,33 @@ class SlicePipeline:
         R, cap = rs.slice.rows, rs.slice.out_len_max
         others = [] if held is None else [self.free_packed.get() for _ in range(self.depth - 1)]
         try:
-            for ptr in [getattr(self, "d_out", 0)] + list(getattr(self, "d_packed", [])):
-                if ptr:
-                    ctx.free(ptr)
-            self.d_out, self.d_packed, self.cap = 0, [], None
+            self._free_rings()
             self.d_out = ctx.malloc(R * rs.out_pitch * 4)
-            self.d_packed = [ctx.malloc(R * cap * 8) for _ in range(self.depth)]
+            for _ in range(self.depth):                    # one at a time: a failed allocation frees those it has made
+                self.d_packed.append(ctx.malloc(R * cap * 8))
             ctx.synchronize()
             self.cap = cap
+        except BaseException:
+            self._free_rings()
+            raise
         finally:                                           # (an allocation that fails must not strand the ring's indices)
             for j in (range(self.depth) if held is None else others):
                 self.free_packed.put(j)
 
+    def _free_rings(self):
+        for ptr in [self.d_out] + self.d_packed:
+            if ptr:
+                self.ctxs[0].free(ptr)
+        self.d_out, self.d_packed, self.cap = 0, [], None
+
+    def _ring(self, j):
+        """(row block, hand-over buffer j) for the slice's present capacity: the rings are re-made when it has changed - the
+        slice grown in mid-measurement or by a job that left its rows on the device - or a re-make failed"""
+        if self.cap != self.rs.slice.out_len_max:
+            self._rings(held=j)
+        return self.d_out, self.d_packed[j]
+
     def _compute(self):
-        from .pipeline_slice import run_slice
         est, layout = self.estimator, self.layout
         try:
             ctx = self.ctxs[0] = _native.Context(self.device)
@@ -757,75 +806,33 @@ class SlicePipeline:
                 job = self.jobs[0].get()
                 if job is None:
                     break
-                host = job["to_host"]
-                bits = job["bit_depth"] if job["output"] == "pcm" else None
                 try:
-                    rs.set_firs(_firs_for(job["firs"], layout, ctx))
-                    rs.set_decay(job["decay"])
-                    rs.set_alignment(job["align"])
-                    _set_vbass(rs, job["vbass"])
+                    rs.apply(job)
                 except BaseException as exc:               # noqa: BLE001
                     self._fail(job, exc)
-                for _ in range(len(job["measurements"])):
+                for _ in range(job["n"]):
                     t0 = time.perf_counter()
-                    i, k, recs, ok = self.uploaded.get()
+                    i, k, recs = self.uploaded.get()
+                    j = self.free_packed.get() if job["to_host"] else None
                     t1 = time.perf_counter()
-                    j = self.free_packed.get() if host else None
-                    t2 = t3 = t4 = time.perf_counter()
-                    out = None
-                    try:
-                        if not ok or job["error"] is not None:
-                            raise _Skip()
-
-                        def once():
-                            if not host:
-                                return rs.execute_device(self.d_rec[k], 1)
-                            if self.cap != rs.slice.out_len_max:      # grown by a job that left its rows on the device, or a failed re-make
-                                self._rings(held=j)
-                            rs.execute_device(self.d_rec[k], 1, self.d_out)
-                            if bits:
-                                rs.slice.pack_pcm(self.d_out, rs.out_pitch, 1, bits, self.d_packed[j], rs.slice.rows * self.cap)
-                            else:
-                                rs.slice.pack_f64(self.d_out, rs.out_pitch, 1, self.d_packed[j], rs.slice.rows * self.cap)
-                            return None
-
-                        block = once()
-                        t3 = time.perf_counter()
-                        rows, meas = rs.slice.results()
-                        t4 = time.perf_counter()
-                        if np.any(meas["flags"] & _native.SLICE_KEEP_CAP) and rs.grow_for(rows):
-                            if j is not None:
-                                self._rings(held=j)
-                            block = once()
-                            rows, meas = rs.slice.results()
-                        if int(meas["flags"][0]) & _native.SLICE_REDO:
-                            rs.stats["measurements"] += 1
-                            rs.stats["staged"] += 1
-                            jobs = [((est.fs, np.asarray(fr)), spec[2], None) for fr, spec in zip(recs, layout.files)]
-                            res = run_slice(est, jobs, head_ms=self.head_ms, peak_target=self.peak_target, firs=job["firs"],
-                                            decay=job["decay"], align=job["align"], vbass=job["vbass"])
-                            if bits:
-                                res = _staged_pcm(res, layout, bits)
-                            elif host:
-                                res[0].to_host()
-                            out = ("result", res)
-                        elif host:
-                            out = ("packed", j, rows, meas, recs, bits)
-                            j = None
-                        else:
-                            out = ("result", rs.collect(block, [recs])[0])
-                    except _Skip:
-                        pass
-                    except BaseException as exc:           # noqa: BLE001
-                        self._fail(job, exc)
-                    self.free_rec.put(k)
+                    t = dict(launch=0.0, wait=0.0)
+                    res = packed = None
+                    if job["error"] is None:
+                        try:
+                            res, packed = rs.measure(self.d_rec[k], recs, job, lambda: self._ring(j), t)
+                            if packed is not None:         # the download stage copies it out and hands j back
+                                packed, j = (j,) + packed + (recs,), None
+                        except BaseException as exc:       # noqa: BLE001
+                            self._fail(job, exc)
+                    if k is not None:
+                        self.free_rec.put(k)
                     if j is not None:
                         self.free_packed.put(j)
-                    self._add(compute_stall=(t1 - t0) + (t2 - t1), launch=t3 - t2, wait=t4 - t3, measurements=1)
-                    self.packed.put((job, i, out))
-            for ptr in self.d_rec + [getattr(self, "d_out", 0)] + list(getattr(self, "d_packed", [])):
-                if ptr:
-                    ctx.free(ptr)
+                    self._add(compute_stall=t1 - t0, measurements=1, **t)
+                    self.packed.put((job, i, res, packed))
+            for ptr in self.d_rec:
+                ctx.free(ptr)
+            self._free_rings()
             rs.close()
             est._forget_context(ctx)
         ctx.close()
@@ -839,33 +846,18 @@ class SlicePipeline:
                 item = self.packed.get()
                 if item is None:
                     break
-                job, i, out = item
-                t1 = t2 = time.perf_counter()
+                job, i, res, packed = item
+                t1 = time.perf_counter()
+                t = dict(to_host=0.0, collect=0.0)
                 try:
-                    if out is None:
-                        pass
-                    elif out[0] == "result":
-                        job["out"][i] = out[1]
-                    else:
-                        _, j, rows, meas, recs, bits = out
-                        try:
-                            R, n = self.rs.slice.rows, int(meas["out_len"][0])
-                            if bits:
-                                flat = _take_words(self.pool, ctx, R * n)
-                            else:
-                                blk = self.pool.take(ctx, R * n)
-                                flat = np.asarray(blk)[:R * n] if blk is not None else np.empty(R * n)
-                            ctx.d2h(flat, self.d_packed[j])
-                        finally:
-                            self.free_packed.put(j)
-                        t2 = time.perf_counter()
-                        if bits:
-                            job["out"][i] = self.rs.collect_pcm(flat.reshape(n, R), rows, meas, bits)
-                        else:
-                            job["out"][i] = self.rs.collect_host(flat.reshape(R, n), rows, meas, [recs])
+                    if packed is not None:
+                        j, rows, meas, recs = packed
+                        res = self.rs.copy_out(self.pool, ctx, self.d_packed[j], rows, meas, [recs], job["bits"],
+                                               release=lambda: self.free_packed.put(j), times=t)
+                    job["out"][i] = res
                 except BaseException as exc:               # noqa: BLE001
                     self._fail(job, exc)
-                self._add(download_stall=t1 - t0, to_host=t2 - t1, collect=time.perf_counter() - t2)
+                self._add(download_stall=t1 - t0, **t)
                 job["left"] -= 1
                 if job["left"] == 0:
                     job["done"].set()
@@ -874,14 +866,9 @@ class SlicePipeline:
     def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None, output="hrir", bit_depth=32):
         """[(HRIR, gain dB)] in the order of `measurements` ([[frames of file 0, ...], ...]); firs, to_host, decay, align,
         vbass, output and bit_depth as SliceRunner.run"""
-        _check_output(output, bit_depth, to_host)
-        _check_vbass(self.estimator.fs, vbass)
-        if not len(measurements):
+        job = _slice_job(self.estimator.fs, measurements, firs, to_host, decay, align, vbass, output, bit_depth)
+        if not job["n"]:
             return []
-        import threading
-        job = dict(measurements=measurements, firs=firs, to_host=to_host, decay=decay, align=align, vbass=vbass, output=output,
-                   bit_depth=int(bit_depth), out=[None] * len(measurements), left=len(measurements), error=None,
-                   done=threading.Event())
         with self._submit:                                 # jobs of concurrent callers enter both stage queues in one order
             for q in self.jobs:
                 q.put(job)
@@ -922,6 +909,7 @@ class SliceFleet:
     cache; FIRs a design left on the first device reach the others as host taps, once per job."""
 
     def __init__(self, estimator, layout, devices=None, **kw):
+        self.estimator = estimator
         self.devices = list(_native.device_list() if devices is None else devices)
         self.pipes = []
         try:
@@ -934,8 +922,7 @@ class SliceFleet:
     def run(self, measurements, firs, to_host=True, decay=None, align=False, vbass=None, output="hrir", bit_depth=32):
         from concurrent.futures import ThreadPoolExecutor
         from .sharding import shard_channels
-        _check_output(output, bit_depth, to_host)
-        n = len(measurements)
+        n = _slice_job(self.estimator.fs, measurements, firs, to_host, decay, align, vbass, output, bit_depth)["n"]
         blocks = [(k,) + shard_channels(n, len(self.pipes), k, keep_pairs=False) for k in range(len(self.pipes))]
         blocks = [(k, lo, hi) for k, lo, hi in blocks if hi > lo]
         kw = dict(to_host=to_host, decay=decay, align=align, vbass=vbass, output=output, bit_depth=bit_depth)
@@ -963,17 +950,12 @@ class SliceFleet:
         self.pipes = []
 
 
-class _Skip(Exception):
-    """a measurement of a job that has already failed: passed through the stages untouched"""
-
-
 def run_slice_jobs(estimator, layout, measurements, firs, workers=None, head_ms=1, peak_target=-0.1, decay=None, align=False,
                    vbass=None, output="hrir", bit_depth=32):
     """one job through a runner made for it (responses on the host): a three-stage SlicePipeline per device of
     IMPULSE_HIP_DEVICES (SliceFleet), or with `workers` that many SliceRunner lanes; callers with several jobs keep a runner.
     output="pcm": [(BrirFrames, gain dB)], as SliceRunner.run"""
-    _check_output(output, bit_depth, True)
-    _check_vbass(estimator.fs, vbass)
+    _slice_job(estimator.fs, measurements, firs, True, decay, align, vbass, output, bit_depth)
     if workers is None:
         runner = SliceFleet(estimator, layout, head_ms=head_ms, peak_target=peak_target)
     else:
@@ -985,26 +967,22 @@ def run_slice_jobs(estimator, layout, measurements, firs, workers=None, head_ms=
         runner.close()
 
 
-def _check_output(output, bit_depth, to_host):
-    """a runner's `output` / `bit_depth` arguments, refused in the caller's thread before any device work"""
+def _slice_job(fs, measurements, firs, to_host=True, decay=None, align=False, vbass=None, output="hrir", bit_depth=32):
+    """A runner's job: its arguments refused in the caller's thread before any device work, then the record every runner
+    serves it from - n measurements, bits (PCM words of that depth; None: float64 rows), out (results in job order), next
+    (the lanes' shared counter), left / error / done (the pipeline's completion)"""
+    import threading
     from .brir_frames import check_bit_depth
     if output not in ("hrir", "pcm"):
         raise ValueError(f"output must be 'hrir' or 'pcm', got {output!r}")
     check_bit_depth(bit_depth)
     if output == "pcm" and not to_host:
         raise ValueError("output='pcm' brings PCM words to the host: it needs to_host=True")
-
-
-def _take_words(pool, ctx, words):
-    """int32 [words] in a block of the runner's page-locked pool (ordinary memory beyond its limit)"""
-    blk = pool.take(ctx, -(-words // 2))
-    return np.asarray(blk).view(np.int32)[:words] if blk is not None else np.empty(words, dtype=np.int32)
-
-
-def _staged_pcm(res, layout, bits):
-    """(BrirFrames, gain dB) of a staged-path result: its rows quantised by the host codec in slice column order"""
-    from .brir_frames import BrirFrames
-    return BrirFrames.from_hrir(res[0], layout.tasks, bits), res[1]
+    _check_vbass(fs, vbass)
+    n = len(measurements)
+    return dict(measurements=measurements, n=n, firs=firs, to_host=to_host, decay=decay, align=align, vbass=vbass,
+                bits=int(bit_depth) if output == "pcm" else None, out=[None] * n, next=0, left=n, error=None,
+                done=threading.Event())
 
 
 def vbass_options(fs, crossover_freq=250, head_ms=1.0, hp_freq=15.0, invert_polarity=None):
@@ -1041,13 +1019,6 @@ def _check_vbass(fs, vbass):
     if unknown:
         raise ValueError(f"vbass: unknown options {sorted(unknown)}")
     vbass_options(fs, **vbass)
-
-
-def _set_vbass(rs, vbass):
-    if vbass is None:
-        rs.set_virtual_bass(None)
-    else:
-        rs.set_virtual_bass(**vbass)
 
 
 def _fir_taps(fs):

@@ -624,3 +624,38 @@ def test_wav_measurements_read_files_and_directories(tmp_path):
     empty.mkdir()
     with pytest.raises(ValueError, match="No HRIR recordings"):
         WavMeasurements.from_dirs([str(empty)])
+
+
+def test_slice_pipeline_rings_keep_nothing_after_a_failed_allocation():
+    """SlicePipeline._rings allocates the row block and the hand-over ring one buffer at a time: when an allocation fails
+    (here the third), the buffers already made are freed and every ring index is back in the free queue"""
+    import queue
+    import types
+    from impulse_hip.resident_slice import SlicePipeline
+
+    class Ctx:
+        def __init__(self):
+            self.made, self.freed = [], []
+
+        def malloc(self, nbytes):
+            if len(self.made) == 2:
+                raise MemoryError("the third allocation")
+            self.made.append(0x1000 * (len(self.made) + 1))
+            return self.made[-1]
+
+        def free(self, ptr):
+            self.freed.append(ptr)
+
+        def synchronize(self):
+            pass
+
+    ctx = Ctx()
+    pipe = SlicePipeline.__new__(SlicePipeline)
+    pipe.rs = types.SimpleNamespace(slice=types.SimpleNamespace(rows=4, out_len_max=100), out_pitch=128)
+    pipe.ctxs, pipe.depth, pipe.free_packed = [ctx, None, None], 3, queue.Queue()
+    pipe.d_out, pipe.d_packed, pipe.cap = 0, [], None
+    with pytest.raises(MemoryError):
+        pipe._rings()
+    assert len(ctx.made) == 2 and sorted(ctx.freed) == ctx.made
+    assert (pipe.d_out, pipe.d_packed, pipe.cap) == (0, [], None)
+    assert sorted(pipe.free_packed.get_nowait() for _ in range(3)) == [0, 1, 2] and pipe.free_packed.empty()

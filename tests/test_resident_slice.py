@@ -845,6 +845,61 @@ def test_job_from_wav_files_on_disk(tmp_path):
         WavMeasurements([[odd]])[0]
 
 
+def test_a_file_the_slice_cannot_read_fails_its_job_not_the_runner(tmp_path):
+    """A WavMeasurements job whose second measurement is a 24-bit file: SlicePipeline.run, SliceRunner.run and
+    run_measurement_dirs (a SliceFleet) raise the ValueError that names the file; the same pipeline then gives the staged
+    path's results for a good job, and every runner closes.  run and close go through a helper thread with a time limit, so
+    a stage that dies fails the test instead of hanging it."""
+    import threading
+    from impulse_hip.audio_io import write_wav_frames
+    from impulse_hip.impulse_response_estimator import ImpulseResponseEstimator
+    from impulse_hip.pipeline_slice import run_measurement_dirs, run_slice
+    from impulse_hip.resident_slice import SlicePipeline, SliceRunner, WavMeasurements, _fir_taps
+
+    def within(fn, limit=300):
+        box = {}
+
+        def call():
+            try:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    box["value"] = fn()
+            except BaseException as exc:                   # noqa: BLE001 - checked by the caller
+                box["error"] = exc
+        th = threading.Thread(target=call, daemon=True)
+        th.start()
+        th.join(limit)
+        assert not th.is_alive(), f"{fn} did not return within {limit} s"
+        return box
+
+    fs = 48000
+    e = ImpulseResponseEstimator(min_duration=1.0, fs=fs)
+    spk = ["FL", "FR"]
+    dirs, paths = [], []
+    for m in range(3):
+        d = tmp_path / f"measurement{m}"
+        d.mkdir()
+        write_wav_frames(str(d / "FL,FR.wav"), fs, synth_frames(e, spk, 2100 + m), 24 if m == 1 else 32)
+        dirs.append(str(d))
+        paths.append([str(d / "FL,FR.wav")])
+    bad = WavMeasurements(paths, fs=fs)
+    layout = bad.layout(e, [spk])
+    firs = synth_firs(layout.tasks, _fir_taps(fs), 37)
+    for cls, kw in ((SlicePipeline, {}), (SliceRunner, dict(workers=2))):
+        runner = cls(e, layout, **kw)
+        got = within(lambda: runner.run(bad, firs))
+        assert isinstance(got.get("error"), ValueError) and paths[1][0] in str(got["error"]), got
+        if cls is SlicePipeline:
+            good = WavMeasurements([paths[0], paths[2]], fs=fs)
+            got = within(lambda: runner.run(good, firs))
+            assert "error" not in got, got
+            for m, p in enumerate((paths[0], paths[2])):
+                assert_same_as_staged(got["value"][m], run_slice(e, [(p[0], spk)], firs=firs))
+        assert within(runner.close) == {"value": None}
+    got = within(lambda: run_measurement_dirs(e, dirs))
+    assert isinstance(got.get("error"), ValueError) and paths[1][0] in str(got["error"]), got
+
+
 def test_firs_left_on_the_device_are_the_same_firs():
     """process_equalization_batch(on_device=True) leaves the minimum-phase FIRs on the device (core/pipeline.py:690-691 hands
     every FIR straight to ImpulseResponse.equalize: they never need to visit the host): the rows are the host version's bits,
