@@ -23,6 +23,7 @@
 #include "decay_kernels.hip.h"      // it switches fp contraction off for what follows
 #include "slice_kernels.hip.h"
 #include "vbass_kernels.hip.h"
+#include "micdev_kernels.hip.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -1591,6 +1592,238 @@ extern "C" int imp_peak_index(imp_ctx* ctx, const float* x, const int64_t* off, 
     }
   }
   rc = peak_index_impl(ctx, d_x, off, len, B, peak_height, idx_out, maxabs_out);
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)ctx_block_put(ctx, d_x);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// K14 microphone-deviation analysis: direct-sound power on the log grid, interaural mismatch per group
+// ------------------------------------------------------------------------------------------------
+// scipy.fft.next_fast_len(n) (real=False): the smallest 2^a 3^b 5^c 7^d 11^e >= n
+static int64_t next_fast_len_11(int64_t n) {
+  for (int64_t m = n < 1 ? 1 : n;; ++m) {
+    int64_t r = m;
+    for (int64_t p : {2, 3, 5, 7, 11})
+      while (r % p == 0) r /= p;
+    if (r == 1) return m;
+  }
+}
+
+// the bins np.interp(grid, rfftfreq(nfft, 1 / fs), mag, left=mag[0], right=mag[-1]) reads, and its brackets
+static void mic_tables(int64_t nfft, double fs, const double* grid, int64_t M, std::vector<long long>& bins,
+                       std::vector<imp::MicInterp>& interp) {
+  const int64_t nxp = nfft / 2 + 1;
+  const double val = 1.0 / ((double)nfft * (1.0 / fs));            // rfftfreq: k * (1 / (n d))
+  auto xp = [&](int64_t k) { return (double)k * val; };
+  std::vector<int64_t> lo((size_t)M), hi((size_t)M);
+  std::vector<int> lerp((size_t)M, 0);
+  std::vector<double> xd((size_t)M, 0.0), dd((size_t)M, 1.0);
+  std::vector<int64_t> used;
+  for (int64_t g = 0; g < M; ++g) {
+    const double x = grid[g];
+    int64_t j;                                                       // binary_search_with_guess: xp[j] <= x < xp[j + 1]
+    if (x < xp(0)) j = -1;
+    else if (x > xp(nxp - 1)) j = nxp;
+    else {
+      j = std::min<int64_t>(std::max<int64_t>((int64_t)std::floor(x / val), 0), nxp - 1);
+      while (j > 0 && xp(j) > x) --j;
+      while (j + 1 < nxp && xp(j + 1) <= x) ++j;
+    }
+    int64_t a = j, b = j;
+    if (j < 0) a = b = 0;
+    else if (j >= nxp - 1) a = b = nxp - 1;                          // right value, or the last bin itself
+    else if (xp(j) != x) {
+      b = j + 1;
+      lerp[(size_t)g] = 1;
+      xd[(size_t)g] = x - xp(j);
+      dd[(size_t)g] = xp(j + 1) - xp(j);
+    }
+    lo[(size_t)g] = a;
+    hi[(size_t)g] = b;
+    used.push_back(a);
+    used.push_back(b);
+  }
+  std::sort(used.begin(), used.end());
+  used.erase(std::unique(used.begin(), used.end()), used.end());
+  bins.assign(used.begin(), used.end());
+  interp.resize((size_t)M);
+  for (int64_t g = 0; g < M; ++g) {
+    imp::MicInterp& e = interp[(size_t)g];
+    e.ia = (int)(std::lower_bound(used.begin(), used.end(), lo[(size_t)g]) - used.begin());
+    e.ib = (int)(std::lower_bound(used.begin(), used.end(), hi[(size_t)g]) - used.begin());
+    e.lerp = lerp[(size_t)g];
+    e.pad = 0;
+    e.xd = xd[(size_t)g];
+    e.dd = dd[(size_t)g];
+  }
+}
+
+template <class T>
+static int mic_mismatch_impl(imp_ctx* ctx, const char* who, const T* d_x, const int64_t* off, const int64_t* len,
+                             const int64_t* peak, const int32_t* group, const int32_t* side, const int32_t* anchor, int64_t B,
+                             int64_t G, int64_t win, int64_t pre, double fs, const double* grid, int64_t M, double* raw_out,
+                             double* power_out) {
+  // rows: the reference's segment and fades; one table set per distinct nfft
+  std::vector<imp::MicRow> rows((size_t)B);
+  std::map<int64_t, size_t> set_of;                                  // nfft -> set
+  std::vector<std::vector<long long>> set_bins;
+  std::vector<std::vector<imp::MicInterp>> set_interp;
+  for (int64_t b = 0; b < B; ++b) {
+    imp::MicRow& r = rows[(size_t)b];
+    const int64_t n = len[b];
+    const int64_t pk = std::min<int64_t>(std::max<int64_t>(peak[b], 0), std::max<int64_t>(n - 1, 0));   // np.clip(peak, 0, n - 1)
+    const int64_t start = std::max<int64_t>(pk - pre, 0), end = std::min<int64_t>(pk + win, n);
+    const int64_t L = n > 0 ? std::max<int64_t>(end - start, 0) : 0;
+    r.off = off[b];
+    r.start = start;
+    r.L = L;
+    r.fade_in = std::min<int64_t>(pre, L / 4);
+    r.fade_out = std::max<int64_t>(L / 4, 1);
+    r.nfft = next_fast_len_11(std::max<int64_t>(L, 8192));
+    r.group = group[b];
+    r.side = side[b];
+    r.anchor = anchor[b] != 0;
+    r.pad = 0;
+    if (L >= imp::kMicMinSeg && !set_of.count(r.nfft)) {
+      set_of[r.nfft] = set_bins.size();
+      set_bins.emplace_back();
+      set_interp.emplace_back();
+      mic_tables(r.nfft, fs, grid, M, set_bins.back(), set_interp.back());
+    }
+  }
+  std::vector<long long> bin_off(set_bins.size());
+  int64_t n_bins = 0, pitch = 1;
+  for (size_t s = 0; s < set_bins.size(); ++s) {
+    bin_off[s] = n_bins;
+    n_bins += (int64_t)set_bins[s].size();
+    pitch = std::max<int64_t>(pitch, (int64_t)set_bins[s].size());
+  }
+  int64_t max_nb = 0;
+  for (auto& r : rows) {
+    if (r.L >= imp::kMicMinSeg) {
+      const size_t s = set_of[r.nfft];
+      r.bin_off = bin_off[s];
+      r.nb = (int64_t)set_bins[s].size();
+      r.interp_off = (long long)s * M;
+    } else {
+      r.bin_off = r.nb = r.interp_off = 0;
+    }
+    max_nb = std::max<int64_t>(max_nb, r.nb);
+  }
+  // staged tables: rows | bins | interp (each 256-byte aligned)
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t rows_b = up((size_t)B * sizeof(imp::MicRow)), bins_b = up((size_t)std::max<int64_t>(n_bins, 1) * sizeof(long long));
+  const size_t interp_b = up(std::max<size_t>(set_bins.size(), 1) * (size_t)M * sizeof(imp::MicInterp));
+  char *h_tab = nullptr, *d_tab = nullptr;
+  int rc = ctx_stage(ctx, rows_b + bins_b + interp_b, (void**)&h_tab, (void**)&d_tab);
+  if (rc) return rc;
+  std::memcpy(h_tab, rows.data(), (size_t)B * sizeof(imp::MicRow));
+  for (size_t s = 0; s < set_bins.size(); ++s) {
+    std::memcpy(h_tab + rows_b + (size_t)bin_off[s] * sizeof(long long), set_bins[s].data(), set_bins[s].size() * sizeof(long long));
+    std::memcpy(h_tab + rows_b + bins_b + s * (size_t)M * sizeof(imp::MicInterp), set_interp[s].data(),
+                (size_t)M * sizeof(imp::MicInterp));
+  }
+  if ((rc = ctx_stage_push(ctx, h_tab, d_tab, rows_b + bins_b + interp_b))) return rc;
+  const imp::MicRow* d_rows = (const imp::MicRow*)d_tab;
+  const long long* d_bins = (const long long*)(d_tab + rows_b);
+  const imp::MicInterp* d_interp = (const imp::MicInterp*)(d_tab + rows_b + bins_b);
+  // work: mag [B][pitch] | power [B][M] | raw [G][M]
+  const size_t mag_n = (size_t)B * (size_t)pitch, pow_n = (size_t)B * (size_t)M, raw_n = (size_t)G * (size_t)M;
+  double* d_work = nullptr;
+  if ((rc = ctx_block_get(ctx, (mag_n + pow_n + raw_n) * sizeof(double), (void**)&d_work))) return rc;
+  double *d_mag = d_work, *d_pow = d_work + mag_n, *d_raw = d_pow + pow_n;
+  hipStream_t s = ctx->stream;
+  const unsigned mblocks = (unsigned)((M + imp::kMicThreads - 1) / imp::kMicThreads);
+  hipError_t e = hipSuccess;
+  if (max_nb > 0) {
+    hipLaunchKernelGGL(imp::micdev_mag_kernel<T>, dim3((unsigned)((max_nb + imp::kMicThreads - 1) / imp::kMicThreads), (unsigned)B),
+                       dim3(imp::kMicThreads), 0, s, d_x, d_rows, d_bins, d_mag, (long long)pitch);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(imp::micdev_power_kernel, dim3(mblocks, (unsigned)B), dim3(imp::kMicThreads), 0, s, d_rows, d_interp,
+                       (const double*)d_mag, (long long)pitch, (long long)M, d_pow);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(imp::micdev_ratio_kernel, dim3(mblocks, (unsigned)G), dim3(imp::kMicThreads), 0, s, d_rows, (long long)B,
+                       (const double*)d_pow, (long long)M, d_raw);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(raw_out, d_raw, raw_n * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && power_out) e = hipMemcpyAsync(power_out, d_pow, pow_n * sizeof(double), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  (void)ctx_block_put(ctx, d_work);
+  if (e != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+  if (e2 != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e2));
+  return IMP_OK;
+}
+
+// the arguments both entries share, refused with the reason; *extent = elements the rows span (max off + len)
+static int mic_check(const char* who, const void* x, const int64_t* off, const int64_t* len, const int64_t* peak,
+                     const int32_t* group, const int32_t* side, const int32_t* anchor, int64_t B, int64_t G, int64_t win,
+                     int64_t pre, double fs, const double* grid, int64_t M, const double* raw_out, int64_t* extent) {
+  if (!off || !len || !peak || !group || !side || !anchor || !grid || !raw_out)
+    return fail(IMP_ERR_INVALID, "%s: null argument", who);
+  if (B < 2 || G < 1 || G > 65535 || B > 65535) return fail(IMP_ERR_INVALID, "%s: B = %lld rows in G = %lld groups (need 2 <= B, 1 <= G, both <= 65535)", who, (long long)B, (long long)G);
+  if (M < 2 || M > (1 << 20)) return fail(IMP_ERR_INVALID, "%s: grid of %lld points (need 2 .. 2^20)", who, (long long)M);
+  if (!(fs > 0.0) || !std::isfinite(fs)) return fail(IMP_ERR_INVALID, "%s: fs must be positive and finite (got %g)", who, fs);
+  if (win < 1 || pre < 0 || win > ((int64_t)1 << 30) || pre > ((int64_t)1 << 30))
+    return fail(IMP_ERR_INVALID, "%s: win = %lld, pre = %lld (need win >= 1, pre >= 0, both <= 2^30)", who, (long long)win, (long long)pre);
+  for (int64_t g = 0; g < M; ++g)
+    if (!std::isfinite(grid[g]) || !(grid[g] > 0.0) || (g && !(grid[g] > grid[g - 1])))
+      return fail(IMP_ERR_INVALID, "%s: grid must be positive, finite and increasing (point %lld)", who, (long long)g);
+  std::vector<int> seen((size_t)G * 2, 0);
+  int64_t ext = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "%s: negative offset/length in row %lld", who, (long long)b);
+    if (group[b] < 0 || group[b] >= G) return fail(IMP_ERR_INVALID, "%s: row %lld names group %d of %lld", who, (long long)b, group[b], (long long)G);
+    if (side[b] != 0 && side[b] != 1) return fail(IMP_ERR_INVALID, "%s: row %lld has side %d (0 left, 1 right)", who, (long long)b, side[b]);
+    if (anchor[b]) seen[(size_t)group[b] * 2 + side[b]] = 1;
+    ext = std::max<int64_t>(ext, off[b] + len[b]);
+  }
+  for (int64_t g = 0; g < G; ++g)
+    if (!seen[(size_t)g * 2] || !seen[(size_t)g * 2 + 1])
+      return fail(IMP_ERR_INVALID, "%s: group %lld has no anchor row for the %s ear", who, (long long)g, seen[(size_t)g * 2] ? "right" : "left");
+  if (ext > 0 && !x) return fail(IMP_ERR_INVALID, "%s: null rows", who);
+  *extent = ext;
+  return IMP_OK;
+}
+
+extern "C" int imp_mic_mismatch_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, const int64_t* peak,
+                                       const int32_t* group, const int32_t* side, const int32_t* anchor, int64_t B, int64_t G,
+                                       int64_t win, int64_t pre, double fs, const double* grid, int64_t M, double* raw_out,
+                                       double* power_out) {
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_mic_mismatch_device: null ctx");
+  IMP_CTX_LOCK(ctx);
+  int64_t ext = 0;
+  int rc = mic_check("imp_mic_mismatch_device", d_x, off, len, peak, group, side, anchor, B, G, win, pre, fs, grid, M, raw_out, &ext);
+  if (rc || (rc = ctx_bind(ctx))) return rc;
+  return mic_mismatch_impl<float>(ctx, "imp_mic_mismatch_device", d_x, off, len, peak, group, side, anchor, B, G, win, pre, fs, grid,
+                                  M, raw_out, power_out);
+}
+
+extern "C" int imp_mic_mismatch(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, const int64_t* peak,
+                                const int32_t* group, const int32_t* side, const int32_t* anchor, int64_t B, int64_t G, int64_t win,
+                                int64_t pre, double fs, const double* grid, int64_t M, double* raw_out, double* power_out) {
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_mic_mismatch: null ctx");
+  IMP_CTX_LOCK(ctx);
+  int64_t ext = 0;
+  int rc = mic_check("imp_mic_mismatch", x, off, len, peak, group, side, anchor, B, G, win, pre, fs, grid, M, raw_out, &ext);
+  if (rc || (rc = ctx_bind(ctx))) return rc;
+  double* d_x = nullptr;
+  if ((rc = ctx_block_get(ctx, (size_t)std::max<int64_t>(ext, 1) * sizeof(double), (void**)&d_x))) return rc;
+  if (ext > 0) {
+    hipError_t e = hipMemcpyAsync(d_x, x, (size_t)ext * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(ctx->stream);
+      (void)ctx_block_put(ctx, d_x);
+      return fail(IMP_ERR_HIP, "imp_mic_mismatch: h2d: %s", hipGetErrorString(e));
+    }
+  }
+  rc = mic_mismatch_impl<double>(ctx, "imp_mic_mismatch", d_x, off, len, peak, group, side, anchor, B, G, win, pre, fs, grid, M,
+                                 raw_out, power_out);
   (void)hipStreamSynchronize(ctx->stream);
   (void)ctx_block_put(ctx, d_x);
   return rc;

@@ -183,6 +183,10 @@ SIGNATURES = {
     "imp_debug_fft64": (C.c_int, [_vp, _pd, _i64, _i64, C.c_int, _pd, C.POINTER(C.c_int)]),
     "imp_peak_index": (C.c_int, [_vp, _pf, _pi64, _pi64, _i64, C.c_double, _pi64, _pf]),
     "imp_peak_index_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, C.c_double, _pi64, _pf]),
+    "imp_mic_mismatch_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _pi64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i64, _i64,
+                                          _i64, _i64, C.c_double, _pd, _i64, _pd, _pd]),
+    "imp_mic_mismatch": (C.c_int, [_vp, _pd, _pi64, _pi64, _pi64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i64, _i64, _i64, _i64,
+                                   C.c_double, _pd, _i64, _pd, _pd]),
     "imp_apply_window": (C.c_int, [_vp, _pf, _pi64, _pi64, _i64, C.POINTER(WindowParams)]),
     "imp_apply_window_device": (C.c_int, [_vp, _vp, _pi64, _vp, _pi64, _pi64, _i64, C.POINTER(WindowParams)]),
     "imp_segset_create_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, C.POINTER(_vp), _pd]),
@@ -354,6 +358,36 @@ class Context:
         _check(self._lib.imp_peak_index(self._h, _ptr_f(flat), _ptr_i64(offs), _ptr_i64(lens), B,
                                         float(peak_height), _ptr_i64(idx), _ptr_f(mx)))
         return idx, mx
+
+    def mic_mismatch(self, rows, peaks, group, side, anchor, G, win, pre, fs, grid, want_power=False, dptr=None):
+        """K14 (imp_mic_mismatch / imp_mic_mismatch_device): raw interaural mismatch [G, M] of the rows' direct-sound power on
+        `grid`, and the per-row power [B, M] when want_power.  rows: host 1-D arrays (fp64 upload), or with dptr the
+        (offsets, lengths) of fp32 device rows at dptr."""
+        grid = np.ascontiguousarray(grid, dtype=np.float64)
+        peaks = np.ascontiguousarray(peaks, dtype=np.int64)
+        i32 = [np.ascontiguousarray(a, dtype=np.int32) for a in (group, side, anchor)]
+        B, M = len(peaks), len(grid)
+        raw = np.zeros((int(G), M), dtype=np.float64)
+        power = np.zeros((B, M), dtype=np.float64) if want_power else None
+        p32 = [a.ctypes.data_as(C.POINTER(C.c_int32)) for a in i32]
+        tail = (B, int(G), int(win), int(pre), float(fs), grid.ctypes.data_as(_pd), M, raw.ctypes.data_as(_pd),
+                power.ctypes.data_as(_pd) if want_power else None)
+        if dptr is None:
+            rows = [np.asarray(r, dtype=np.float64) for r in rows]
+            lens = np.array([len(r) for r in rows], dtype=np.int64)
+            offs = np.zeros(B, dtype=np.int64)
+            if B:
+                offs[1:] = np.cumsum(lens)[:-1]
+            flat = np.concatenate(rows) if int(lens.sum()) else np.zeros(1)
+            flat = np.ascontiguousarray(flat, dtype=np.float64)
+            _check(self._lib.imp_mic_mismatch(self._h, flat.ctypes.data_as(_pd), _ptr_i64(offs), _ptr_i64(lens), _ptr_i64(peaks),
+                                              *p32, *tail))
+        else:
+            offs = np.ascontiguousarray(rows[0], dtype=np.int64)
+            lens = np.ascontiguousarray(rows[1], dtype=np.int64)
+            _check(self._lib.imp_mic_mismatch_device(self._h, _vp(int(dptr)), _ptr_i64(offs), _ptr_i64(lens), _ptr_i64(peaks),
+                                                     *p32, *tail))
+        return raw, power
 
     # ---- device-resident rows (fp32 at dptr + off[b], len[b] samples) ---------------------------
     @staticmethod

@@ -9,6 +9,7 @@ parity-checked end to end and benchmarked.
 import numpy as np
 
 import threading
+import warnings
 from concurrent.futures import ThreadPoolExecutor
 
 from . import _native
@@ -52,8 +53,26 @@ def _expected_tasks(recordings):
     return out
 
 
+def _check_mic_deviation(mic_deviation):
+    """run_slice's `mic_deviation` argument (None or the keywords correction_strength / anchor), refused before device work"""
+    if mic_deviation is None:
+        return
+    if not isinstance(mic_deviation, dict):
+        raise ValueError(f"mic_deviation must be None or a dict, got {type(mic_deviation).__name__}")
+    unknown = set(mic_deviation) - {"correction_strength", "anchor"}
+    if unknown:
+        raise ValueError(f"mic_deviation: unknown options {sorted(unknown)}")
+    strength = mic_deviation.get("correction_strength", 0.7)
+    if isinstance(strength, (bool, np.bool_)) or not isinstance(strength, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(strength):
+        raise ValueError(f"mic_deviation: correction_strength must be a finite number, got {strength!r}")
+    if not isinstance(mic_deviation.get("anchor", "auto"), str):
+        raise ValueError(f"mic_deviation: anchor must be a string, got {mic_deviation['anchor']!r}")
+
+
 def run_slice(estimator, recordings, room_frs=None, target=None, head_ms=1, decay=None, peak_target=-0.1,
-              hp_left=None, hp_right=None, eq_left=None, eq_right=None, stages=None, firs=None, align=False, vbass=None):
+              hp_left=None, hp_right=None, eq_left=None, eq_right=None, stages=None, firs=None, align=False, vbass=None,
+              mic_deviation=None):
     """recordings: list of (path_or_(fs, array), speakers[, side]) measurement files.
     Returns the HRIR after: ingest (batched GPU deconvolution) -> crop_heads -> crop_tails ->
     per-channel minimum-phase FIR (batched GPU design) + equalize -> optional decay adjustment ->
@@ -67,7 +86,12 @@ def run_slice(estimator, recordings, room_frs=None, target=None, head_ms=1, deca
     align_ipsilateral_all over IPSILATERAL_PAIRS with 30 ms segments, align_onset_groups_peak_leftref); responses that are
     on the device stay there.
     ``vbass``: None, or the keywords of virtual_bass.apply_virtual_bass_to_hrir (crossover_freq, head_ms, hp_freq,
-    invert_polarity): virtual bass between crop_tails and equalize, where the reference runs it (core/pipeline.py:603-616)."""
+    invert_polarity): virtual bass between crop_tails and equalize, where the reference runs it (core/pipeline.py:603-616).
+    ``mic_deviation``: None, or the keywords correction_strength and anchor of
+    microphone_deviation_correction.apply_microphone_deviation_correction_to_hrir: the correction after virtual bass and before
+    equalize (core/pipeline.py:618-635); skipped with a warning when headphone compensation is on (hp_left / hp_right given,
+    core/pipeline.py:429-446)."""
+    _check_mic_deviation(mic_deviation)
     hrir = HRIR(estimator)
     fs = estimator.fs
     common = FrequencyResponse.generate_frequencies(f_min=10, f_max=fs / 2, f_step=1.01)
@@ -104,6 +128,14 @@ def run_slice(estimator, recordings, room_frs=None, target=None, head_ms=1, deca
         from .virtual_bass import apply_virtual_bass_to_hrir
         apply_virtual_bass_to_hrir(hrir, **vbass)
         snap("vbass")
+    if mic_deviation is not None:
+        if hp_left is not None or hp_right is not None:
+            warnings.warn("microphone-deviation correction skipped: headphone compensation cancels the microphones' transfer "
+                          "functions per ear, so the correction would balance the ears twice")
+        else:
+            from .microphone_deviation_correction import apply_microphone_deviation_correction_to_hrir
+            apply_microphone_deviation_correction_to_hrir(hrir, **mic_deviation)
+            snap("mic_deviation")
 
     tasks = [(sp, sd) for sp, pair in hrir.irs.items() for sd in pair]
     if firs is None:

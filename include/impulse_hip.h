@@ -348,6 +348,27 @@ int imp_peak_index(imp_ctx* ctx, const float* x, const int64_t* off, const int64
 int imp_peak_index_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len,
                           int64_t B, double peak_height, int64_t* idx_out, float* maxabs_out);
 
+/* ---- K14: microphone-deviation analysis, fp64 ----------------------------------------------------
+ * core/microphone_deviation_correction.py:106-140 MicrophoneMatchingCorrector._windowed_power for every row and :195-218
+ * estimate_interaural_mismatch up to raw_delta for every group (one HRIR = one group): row b is cut to
+ * [max(p - pre, 0), min(p + win, n)) with p = clip(peak[b], 0, n - 1) and n = len[b]; fewer than 8 samples -> power 0;
+ * fades of min(pre, L // 4) and max(L // 4, 1) samples as halves of np.hanning(2 fade) when > 1; |rfft| at
+ * nfft = scipy.fft.next_fast_len(max(L, 8192)) (11-smooth) evaluated at the bins np.interp(grid, rfftfreq(nfft, 1 / fs),
+ * |X|, left=|X[0]|, right=|X[-1]|) reads, squared.  Group g: mean power of its rows with anchor[b] != 0 per ear (side 0 =
+ * left, 1 = right; summed in row order), raw_out[g][m] = 10 log10((left + 1e-20) / (right + 1e-20)).
+ * win, pre: the reference's max(int(round(window_ms fs / 1000)), 32) and max(int(round(pre_ms fs / 1000)), 0), computed
+ * by the caller (Python rounds half to even).  grid: M positive increasing frequencies (the reference's
+ * generate_frequencies(f_step=1.01, f_min=20, f_max=fs / 2)).  Every group needs an anchor row on each ear.
+ * power_out (may be NULL): [B][M] per-row power.  Arithmetic is fp64 in both entries; the spectrum is a direct sum with
+ * the angle (k n) mod nfft reduced exactly.  Synchronous: the results are on the host when the call returns.
+ * imp_mic_mismatch_device: fp32 device rows at d_x + off[b];  imp_mic_mismatch: fp64 host rows at x + off[b]. */
+int imp_mic_mismatch_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, const int64_t* peak,
+                            const int32_t* group, const int32_t* side, const int32_t* anchor, int64_t B, int64_t G, int64_t win,
+                            int64_t pre, double fs, const double* grid, int64_t M, double* raw_out, double* power_out);
+int imp_mic_mismatch(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, const int64_t* peak,
+                     const int32_t* group, const int32_t* side, const int32_t* anchor, int64_t B, int64_t G, int64_t win,
+                     int64_t pre, double fs, const double* grid, int64_t M, double* raw_out, double* power_out);
+
 /* ---- K6: minimum-phase FIR design, batched, fp64 -----------------------------------------------
  * Tail of FrequencyResponse.minimum_phase_impulse_response (autoeq/frequency_response.py:676-680),
  * called per channel by core/parallel_workers.py:129:
