@@ -2590,22 +2590,44 @@ extern "C" int imp_sosfilt_chunked(imp_ctx* ctx, const double* sos, int64_t n_se
   return IMP_OK;
 }
 
-// K10 on the stream: the lag slices of every pair, then the first maximum over the slices.  lds_doubles = longest a_len + b_len,
-// nk_max = longest a_len + b_len - 1; part_k / part_val: [B * xcorr_slices(nk_max)]
+// K10 on the stream: the lag slices of every pair, then the first maximum over the slices.  lds_doubles = the largest
+// xcorr_lds_doubles(a_len[p], b_len[p]) over the pairs (a's planes are rounded per pair, so it is not a function of
+// a_len + b_len alone), nk_max = longest a_len + b_len - 1; part_k / part_val: [B * xcorr_slices(nk_max)]
+constexpr int64_t kXcorrMaxSamples = 16384;        // a_len + b_len of one pair
+// the dynamic LDS the kernel is opted in to: the largest xcorr_lds_doubles over legal pairs.  A pair (na, kXcorrMaxSamples - na)
+// needs 4 floor((na + 2 kXcorrPad + 3) / 4) + 4 - na + kXcorrMaxSamples, largest where na = 1 (mod 4): 16 911 doubles (135 288 B,
+// plus 3 KB of static LDS).  imp_debug_xcorr_lds checks every legal pair against it.
+static int64_t xcorr_lds_cap() { return imp::xcorr_lds_doubles(1, kXcorrMaxSamples - 1); }
 static int64_t xcorr_slices(int64_t nk_max) {
   const int64_t per = (int64_t)imp::kXcorrThreads * imp::kXcorrLags;
   return std::max<int64_t>(1, (nk_max + per - 1) / per);
+}
+// the pairs' checks and launch size: *nk = longest a_len + b_len, *lds_doubles = what launch_xcorr requests
+static int xcorr_check_pairs(const int64_t* a_off, const int64_t* a_len, const int64_t* b_off, const int64_t* b_len, int64_t B,
+                             int64_t* nk, int64_t* lds_doubles) {
+  *nk = 0;
+  *lds_doubles = 0;
+  for (int64_t p = 0; p < B; ++p) {
+    if (a_len[p] < 1 || b_len[p] < 1 || a_off[p] < 0 || b_off[p] < 0)
+      return fail(IMP_ERR_INVALID, "pair %lld: empty segment or negative offset", (long long)p);   // scipy raises on empty input
+    if (a_len[p] + b_len[p] > kXcorrMaxSamples)
+      return fail(IMP_ERR_UNSUPPORTED, "pair %lld: %lld + %lld samples exceed the 16384 the lag search holds in LDS",
+                  (long long)p, (long long)a_len[p], (long long)b_len[p]);
+    *nk = std::max(*nk, a_len[p] + b_len[p]);
+    *lds_doubles = std::max(*lds_doubles, (int64_t)imp::xcorr_lds_doubles(a_len[p], b_len[p]));
+  }
+  return IMP_OK;
 }
 template <class Sample>
 static int launch_xcorr(imp_ctx* ctx, hipStream_t s, const Sample* a, const int64_t* a_off, const int64_t* a_len, const Sample* b,
                         const int64_t* b_off, const int64_t* b_len, int64_t B, int64_t lds_doubles, int64_t nk_max, long long* part_k,
                         double* part_val, long long* d_arg, double* d_val) {
   int rc;
-  if ((rc = ctx_kernel_lds(ctx, reinterpret_cast<const void*>(imp::xcorr_argmax_kernel<Sample>), (size_t)imp::xcorr_lds_doubles(16384, 0) * sizeof(double))))
+  if ((rc = ctx_kernel_lds(ctx, reinterpret_cast<const void*>(imp::xcorr_argmax_kernel<Sample>), (size_t)xcorr_lds_cap() * sizeof(double))))
     return rc;
   const int64_t S = xcorr_slices(nk_max);
   hipLaunchKernelGGL(imp::xcorr_argmax_kernel<Sample>, dim3((unsigned)B, (unsigned)S), dim3(imp::kXcorrThreads),
-                     (size_t)imp::xcorr_lds_doubles(lds_doubles, 0) * sizeof(double), s, a, a_off, a_len, b, b_off, b_len, part_k, part_val);
+                     (size_t)lds_doubles * sizeof(double), s, a, a_off, a_len, b, b_off, b_len, part_k, part_val);
   hipLaunchKernelGGL(imp::xcorr_reduce_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, (const long long*)part_k, (const double*)part_val, (int)S,
                      (int)B, d_arg, d_val);
   HIP_TRY(hipGetLastError());
@@ -2619,18 +2641,14 @@ extern "C" int imp_xcorr_argmax(imp_ctx* ctx, const double* a, const int64_t* a_
     return fail(IMP_ERR_INVALID, "imp_xcorr_argmax: null argument");
   if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
   if (B == 0) return IMP_OK;
-  int64_t ta = 0, tb = 0, lds = 0;
+  int64_t ta = 0, tb = 0, lds = 0, lds_doubles = 0;
+  int rc = xcorr_check_pairs(a_off, a_len, b_off, b_len, B, &lds, &lds_doubles);
+  if (rc) return rc;
   for (int64_t p = 0; p < B; ++p) {
-    if (a_len[p] < 1 || b_len[p] < 1 || a_off[p] < 0 || b_off[p] < 0)
-      return fail(IMP_ERR_INVALID, "pair %lld: empty segment or negative offset", (long long)p);   // scipy raises on empty input
-    if (a_len[p] + b_len[p] > 16384)
-      return fail(IMP_ERR_UNSUPPORTED, "pair %lld: %lld + %lld samples exceed the 16384 the lag search holds in LDS",
-                  (long long)p, (long long)a_len[p], (long long)b_len[p]);
     ta = std::max(ta, a_off[p] + a_len[p]);
     tb = std::max(tb, b_off[p] + b_len[p]);
-    lds = std::max(lds, a_len[p] + b_len[p]);
   }
-  int rc = ctx_bind(ctx);
+  rc = ctx_bind(ctx);
   if (rc) return rc;
   IMP_CTX_LOCK(ctx);
   hipStream_t s = ctx->stream;
@@ -2653,7 +2671,7 @@ extern "C" int imp_xcorr_argmax(imp_ctx* ctx, const double* a, const int64_t* a_
   HIP_TRY(hipMemcpyAsync(d_meta + B, a_len, meta, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_meta + 2 * B, b_off, meta, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_meta + 3 * B, b_len, meta, hipMemcpyHostToDevice, s));
-  if ((rc = launch_xcorr<double>(ctx, s, d_a, d_meta, d_meta + B, d_b, d_meta + 2 * B, d_meta + 3 * B, B, lds, lds - 1, d_pk, d_pv, d_arg, d_val)))
+  if ((rc = launch_xcorr<double>(ctx, s, d_a, d_meta, d_meta + B, d_b, d_meta + 2 * B, d_meta + 3 * B, B, lds_doubles, lds - 1, d_pk, d_pv, d_arg, d_val)))
     return rc;
   std::vector<long long> h_arg((size_t)B);
   std::vector<double> h_val((size_t)B);
@@ -2673,17 +2691,11 @@ extern "C" int imp_xcorr_argmax_device(imp_ctx* ctx, const float* d_x, const int
     return fail(IMP_ERR_INVALID, "imp_xcorr_argmax_device: null argument");
   if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
   if (B == 0) return IMP_OK;
-  int64_t lds = 0;
-  for (int64_t p = 0; p < B; ++p) {
-    if (a_len[p] < 1 || b_len[p] < 1 || a_off[p] < 0 || b_off[p] < 0)
-      return fail(IMP_ERR_INVALID, "pair %lld: empty segment or negative offset", (long long)p);
-    if (a_len[p] + b_len[p] > 16384)
-      return fail(IMP_ERR_UNSUPPORTED, "pair %lld: %lld + %lld samples exceed the 16384 the lag search holds in LDS",
-                  (long long)p, (long long)a_len[p], (long long)b_len[p]);
-    lds = std::max(lds, a_len[p] + b_len[p]);
-  }
+  int64_t lds = 0, lds_doubles = 0;
+  int rc = xcorr_check_pairs(a_off, a_len, b_off, b_len, B, &lds, &lds_doubles);
+  if (rc) return rc;
   IMP_CTX_LOCK(ctx);
-  int rc = ctx_bind(ctx);
+  rc = ctx_bind(ctx);
   if (rc) return rc;
   hipStream_t s = ctx->stream;
   const size_t meta = (size_t)B * sizeof(int64_t);
@@ -2699,7 +2711,7 @@ extern "C" int imp_xcorr_argmax_device(imp_ctx* ctx, const float* d_x, const int
   HIP_TRY(hipMemcpyAsync(d_meta + B, a_len, meta, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_meta + 2 * B, b_off, meta, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_meta + 3 * B, b_len, meta, hipMemcpyHostToDevice, s));
-  if ((rc = launch_xcorr<float>(ctx, s, d_x, d_meta, d_meta + B, d_x, d_meta + 2 * B, d_meta + 3 * B, B, lds, lds - 1, d_pk, d_pv, d_arg, d_val)))
+  if ((rc = launch_xcorr<float>(ctx, s, d_x, d_meta, d_meta + B, d_x, d_meta + 2 * B, d_meta + 3 * B, B, lds_doubles, lds - 1, d_pk, d_pv, d_arg, d_val)))
     return rc;
   std::vector<long long> h_arg((size_t)B);
   std::vector<double> h_val((size_t)B);
@@ -2710,6 +2722,21 @@ extern "C" int imp_xcorr_argmax_device(imp_ctx* ctx, const float* d_x, const int
     arg_out[p] = (int64_t)h_arg[(size_t)p];
     if (val_out) val_out[p] = h_val[(size_t)p];
   }
+  return IMP_OK;
+}
+
+extern "C" int imp_debug_xcorr_lds(int64_t na, int64_t nb, int64_t* requested, int64_t* needed) {
+  const int64_t off = 0;
+  int64_t nk = 0, lds_doubles = 0;
+  int rc = xcorr_check_pairs(&off, &na, &off, &nb, 1, &nk, &lds_doubles);
+  if (rc) return rc;
+  if (lds_doubles > xcorr_lds_cap())
+    return fail(IMP_ERR_UNSUPPORTED, "(%lld, %lld): the launch requests %lld doubles, over the %lld the lag search is opted in to",
+                (long long)na, (long long)nb, (long long)lds_doubles, (long long)xcorr_lds_cap());
+  // what xcorr_argmax_kernel indexes: four planes of P slots for a, then b at plane + 4 P
+  const int64_t P = (na + 2 * imp::kXcorrPad + 3) / 4 + 1;
+  if (requested) *requested = lds_doubles;
+  if (needed) *needed = 4 * P + nb;
   return IMP_OK;
 }
 

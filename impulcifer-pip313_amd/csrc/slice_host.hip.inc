@@ -645,7 +645,7 @@ extern "C" int imp_slice_execute_device(imp_slice* s, const void* d_rec, int64_t
                          (const int64_t*)s->d_len2, (const int*)s->d_ipsi_a, (const int*)s->d_ipsi_b, s->n_ipsi, (int)R, n_jobs, (long long)s->segment,
                          s->d_xa_off, s->d_xa_len, s->d_xb_off, s->d_xb_len, s->d_flags);
       if ((rc = launch_xcorr<float>(ctx, st, (const float*)s->d_ir, (const int64_t*)s->d_xa_off, (const int64_t*)s->d_xa_len, (const float*)s->d_ir,
-                                    (const int64_t*)s->d_xb_off, (const int64_t*)s->d_xb_len, n_jobs, 2 * s->segment, 2 * s->segment - 1,
+                                    (const int64_t*)s->d_xb_off, (const int64_t*)s->d_xb_len, n_jobs, imp::xcorr_lds_doubles(s->segment, s->segment), 2 * s->segment - 1,
                                     s->d_xpart_k, s->d_xpart_val, s->d_xarg, s->d_xval)))
         return rc;
     }

@@ -156,6 +156,7 @@ SIGNATURES = {
     "imp_debug_plan_geometry": (C.c_int, [_i64, _i64, C.c_int, _pi64, _pi64, _pi64]),
     "imp_debug_plan_geometry_fused": (C.c_int, [_i64, _i64, C.c_int, _pi64, _pi64, _pi64, _pi64]),
     "imp_debug_chain_tail_geometry": (C.c_int, [_i64, _i64, _pi64, _pi64, _pi64]),
+    "imp_debug_xcorr_lds": (C.c_int, [_i64, _i64, _pi64, _pi64]),
     "imp_debug_plan_geometry_paired": (C.c_int, [_i64, _i64, C.c_int, _pi64, _pi64, _pi64, _pi64]),
     "imp_debug_host_spectrum": (C.c_int, [_pd, _i64, C.c_int, _pf]),
     "imp_plan_debug_run_stage": (C.c_int, [_vp, _pf, _i64, _i64, C.c_int, _pf]),
@@ -1412,6 +1413,15 @@ def chain_tail_geometry(M, L):
         return None
     _check(rc)
     return a.value, b.value, c.value
+
+
+def xcorr_lds(na, nb):
+    """(requested, needed): the dynamic LDS in doubles the lag search's launch requests for the pair (na, nb) alone, and
+    the doubles its kernel indexes; raises where the lag search refuses the pair; needs no GPU."""
+    lib = load_library()
+    a, b = _i64(), _i64()
+    _check(lib.imp_debug_xcorr_lds(int(na), int(nb), C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def plan_geometry_paired(M, L, mode="same"):

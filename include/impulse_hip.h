@@ -328,6 +328,10 @@ int imp_xcorr_argmax(imp_ctx* ctx, const double* a, const int64_t* a_off, const 
  * the sums have the bits imp_xcorr_argmax forms from the rows' float64 copies); tables and results are host memory */
 int imp_xcorr_argmax_device(imp_ctx* ctx, const float* d_x, const int64_t* a_off, const int64_t* a_len, const int64_t* b_off,
                             const int64_t* b_len, int64_t B, int64_t* arg_out, double* val_out);
+/* test hook, needs no GPU: for a call whose only pair is (na, nb), the dynamic LDS in doubles the lag search's launch requests
+ * and the doubles its kernel indexes (a's four padded planes, then b); IMP_ERR_INVALID / IMP_ERR_UNSUPPORTED where the two
+ * entry points above refuse the pair, IMP_ERR_UNSUPPORTED too if the request exceeds the size the kernel is opted in to */
+int imp_debug_xcorr_lds(int64_t na, int64_t nb, int64_t* requested, int64_t* needed);
 /* ImpulseResponse.shift (core/impulse_response.py:92-108) for fp32 device rows: row b (len[b] samples at d_src +
  * src_off[b]) delayed by shift[b] > 0 (zeros in front, the tail dropped) or advanced by -shift[b] (the head dropped, zeros
  * behind), length kept, written to d_dst + dst_off[b] (not the source rows).  Asynchronous on the context's stream. */

@@ -614,6 +614,35 @@ def test_minimum_phase_fir_golden(gpu_ctx, golden, fs):
         gpu_ctx.minphase_fir(bad, fs)                            # type II filter needs a Nyquist zero
 
 
+@pytest.mark.parametrize("fs", [44100, 88200, 22050])
+def test_minimum_phase_fir_at_other_rates(golden, fs):
+    """K6 at 44.1, 88.2 and 22.05 kHz (f_res = 5: 9000, 18000 and 4500 taps; transforms of 2n = 18000, 36000 and 9000
+    points, all of radices 2, 3 and 5) against the oracle's fp64 design.  The homomorphic log at the forced Nyquist zero
+    is worse conditioned at these rates than at 48 kHz: 1-ulp changes of five points of the curve move the oracle's own
+    FIR by up to 7.5e-8 of its peak at 44.1 kHz (1.5e-8 at 48 kHz), almost all of it a tone at Nyquist.  So the taps are
+    held to 3e-7 of the peak, the spectrum below 0.9 Nyquist to 1e-6 of its peak, and the design to the curve and to
+    minimum phase as at 48 kHz."""
+    from impulse_hip.frequency_response import minimum_phase_impulse_responses
+    from oracle.minphase import minimum_phase_impulse_response as oracle_fir
+    g = golden("minphase")
+    freq = g["fs48000_freq"]
+    names = ("flat", "wavy", "tilt")
+    firs = minimum_phase_impulse_responses(freq, [g[f"fs48000_{nm}_eq"] for nm in names], fs, f_res=5, normalize=False)
+    for fir, nm in zip(firs, names):
+        want = oracle_fir(freq, g[f"fs48000_{nm}_eq"], fs, f_res=5, normalize=False)
+        assert fir.shape == want.shape == ({44100: 9000, 88200: 18000, 22050: 4500}[fs],)
+        assert np.all(np.isfinite(fir))
+        assert np.max(np.abs(fir - want)) <= 3e-7 * np.max(np.abs(want)), nm
+        D, W = np.abs(np.fft.rfft(fir - want)), np.abs(np.fft.rfft(want))
+        assert np.max(D[:int(0.9 * len(D))]) <= 1e-6 * np.max(W), nm
+        assert np.sum(fir[: len(fir) // 8] ** 2) > 0.9 * np.sum(fir ** 2)
+        f = np.fft.rfftfreq(len(fir) * 4, 1 / fs)
+        H = 20 * np.log10(np.abs(np.fft.rfft(fir, len(fir) * 4)) + 1e-30)
+        from oracle.impulse_response import interpolate_log
+        sel = (f > 50) & (f < fs / 2 * 0.8)
+        assert np.max(np.abs(H[sel] - interpolate_log(freq, g[f"fs48000_{nm}_eq"], f[sel]))) < 0.5, nm
+
+
 def test_minimum_phase_fir_then_equalize_chain(gpu_ctx, golden):
     """EQ curve -> FIR (K6) -> ir.equalize(fir) (K5): the chain of core/pipeline.py:668-691."""
     from impulse_hip.frequency_response import minimum_phase_impulse_response
@@ -978,19 +1007,29 @@ def test_k10_lag_search_matches_scipy_and_oracle(gpu_ctx):
 def test_alignment_matches_reference_run(gpu_ctx, golden):
     """HRIR.align_ipsilateral_all (device lag search) and align_onset_groups_peak_leftref (device peak
     search) against the reference's own run on the seeded nine-speaker set (fixture section 11)."""
+    _alignment_against_reference_run(gpu_ctx, golden("alignment"), 48000)
+
+
+@pytest.mark.parametrize("fs", [44100, 88200])
+def test_alignment_matches_reference_run_at_other_rates(gpu_ctx, golden, fs):
+    """The same at 44.1 and 88.2 kHz (fixture section 11 at those rates): 30 ms segments of 1323 and 2646 samples."""
+    _alignment_against_reference_run(gpu_ctx, golden(f"alignment_fs{fs}"), fs)
+
+
+def _alignment_against_reference_run(gpu_ctx, g, fs):
     from make_goldens import alignment_inputs
     from impulse_hip.hrir import HRIR
     from impulse_hip.impulse_response import ImpulseResponse
-    g = golden("alignment")
-    irs = alignment_inputs()
+    irs = alignment_inputs(fs=fs)
 
     class Est:
-        fs = 48000
+        pass
+    Est.fs = fs
     for name, call in (("ipsi", lambda hh: hh.align_ipsilateral_all()),
                        ("chain", lambda hh: hh.align_ipsilateral_all(speaker_pairs=[("FL", "FR"), ("FR", "SL"), ("SL", "FL")])),
                        ("onset", lambda hh: hh.align_onset_groups_peak_leftref())):
         h = HRIR(Est())
-        h.irs = {sp: {sd: ImpulseResponse(x.copy(), 48000) for sd, x in pair.items()} for sp, pair in irs.items()}
+        h.irs = {sp: {sd: ImpulseResponse(x.copy(), fs) for sd, x in pair.items()} for sp, pair in irs.items()}
         call(h)
         for sp in irs:
             for sd in ("left", "right"):
@@ -1011,8 +1050,8 @@ def test_alignment_matches_reference_run(gpu_ctx, golden):
         gpu_ctx.h2d(block.ptr, flat)
         dev, host = HRIR(Est()), HRIR(Est())
         for i, (sp, sd) in enumerate(names):
-            dev.irs.setdefault(sp, {})[sd] = ImpulseResponse.on_device(Row(block, i * pitch, len(rounded[(sp, sd)])), 48000)
-            host.irs.setdefault(sp, {})[sd] = ImpulseResponse(rounded[(sp, sd)].astype(np.float64), 48000)
+            dev.irs.setdefault(sp, {})[sd] = ImpulseResponse.on_device(Row(block, i * pitch, len(rounded[(sp, sd)])), fs)
+            host.irs.setdefault(sp, {})[sd] = ImpulseResponse(rounded[(sp, sd)].astype(np.float64), fs)
         call(dev)
         call(host)
         for sp, sd in names:

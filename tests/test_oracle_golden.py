@@ -357,6 +357,31 @@ def test_ipsilateral_alignment(golden):
             assert float(np.sum(d)) == float(g[f"onset_{sp}_{sd}_sum"])
 
 
+@pytest.mark.parametrize("fs", [44100, 88200])
+def test_ipsilateral_and_onset_alignment_at_other_rates(golden, fs):
+    """The oracle's align_ipsilateral_all and align_onset_groups_peak_leftref against the reference run at 44.1 and
+    88.2 kHz (fixture section 11 at those rates): 30 ms segments of 1323 and 2646 samples, lengths that are not a
+    multiple of 4 (odd at 44.1 kHz)."""
+    from make_goldens import alignment_inputs
+    from impulse_hip.constants import IPSILATERAL_PAIRS
+    g = golden(f"alignment_fs{fs}")
+    irs = alignment_inputs(fs=fs)
+    for name, run in (("ipsi", lambda x: ohrir.align_ipsilateral_all(x, fs, IPSILATERAL_PAIRS)),
+                      ("chain", lambda x: ohrir.align_ipsilateral_all(x, fs, [("FL", "FR"), ("FR", "SL"), ("SL", "FL")])),
+                      ("onset", ohrir.align_onset_groups_peak_leftref)):
+        out = run(irs)
+        for sp in irs:
+            for sd in ("left", "right"):
+                d = out[sp][sd]
+                assert int(np.argmax(np.abs(d))) == int(g[f"{name}_{sp}_{sd}_peak"]), (name, sp, sd)
+                np.testing.assert_array_equal(d[:96], g[f"{name}_{sp}_{sd}_head"])
+                np.testing.assert_array_equal(d[-96:], g[f"{name}_{sp}_{sd}_tail"])
+                assert float(np.sum(d)) == float(g[f"{name}_{sp}_{sd}_sum"])
+    # the alignment really moves responses at these rates
+    ins = {k: int(np.argmax(np.abs(irs[k[0]][k[1]]))) for k in ((sp, sd) for sp in irs for sd in ("left", "right"))}
+    assert any(int(g[f"ipsi_{sp}_{sd}_peak"]) != p for (sp, sd), p in ins.items())
+
+
 def test_sosfilt_restatement(golden):
     """oracle.virtual_bass.sosfilt against scipy.signal.sosfilt outputs captured in the reference run
     (fixture section 12): the same separately rounded operations, so the same bits."""

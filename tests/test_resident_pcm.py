@@ -315,11 +315,11 @@ CONFIGS = {"plain": (dict(), 32), "align": (dict(align=True), 24), "decay": (dic
            "vbass": (dict(align=True, vbass={}), 32)}
 
 
-def _job(spk, M, seed, seconds=1.0):
+def _job(spk, M, seed, seconds=1.0, fs=48000):
     from test_resident_slice import synth_firs, synth_frames
     from impulse_hip.impulse_response_estimator import ImpulseResponseEstimator
     from impulse_hip.resident_slice import Layout, _fir_taps
-    e = ImpulseResponseEstimator(min_duration=seconds, fs=48000)
+    e = ImpulseResponseEstimator(min_duration=seconds, fs=fs)
     meas = [[synth_frames(e, spk, seed + m, rt60=0.18 + 0.03 * m)] for m in range(M)]
     layout = Layout(e, [(meas[0][0].shape[0], 2, spk)])
     return e, meas, layout, synth_firs(layout.tasks, _fir_taps(e.fs), seed)
@@ -389,6 +389,20 @@ def test_full_size_c2_pcm_files(tmp_path):
             assert_pcm_as_hrir(got[m], want[m], str(tmp_path), 32, f"c2_{m}", _staged(e, meas[m], spk, firs, align=True))
     finally:
         pipe.close()
+
+
+@pytest.mark.gpu
+def test_pcm_files_at_44k1(tmp_path):
+    """run_slice_jobs with output='pcm' at 44.1 kHz with the alignments on (30 ms segments of 1323 samples): the files are
+    HRIR.write_wav's of the same runner's output='hrir' result and of the staged run_slice result, byte for byte"""
+    from impulse_hip.resident_slice import run_slice_jobs
+    spk = ["FL", "FR", "FC", "SL", "SR"]
+    e, meas, layout, firs = _job(spk, 2, 4410, fs=44100)
+    want = _quiet(run_slice_jobs, e, layout, meas, firs, align=True)
+    got = _quiet(run_slice_jobs, e, layout, meas, firs, output="pcm", bit_depth=24, align=True)
+    for m in range(2):
+        assert got[m][0].fs == 44100
+        assert_pcm_as_hrir(got[m], want[m], str(tmp_path), 24, f"fs44100_{m}", _staged(e, meas[m], spk, firs, align=True))
 
 
 @pytest.mark.gpu

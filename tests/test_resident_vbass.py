@@ -130,9 +130,20 @@ def _setup(spk_files, fs=48000, seconds=1.0, M=2, seed=0, max_measurements=None)
 @pytest.mark.gpu
 @pytest.mark.parametrize("opts", VB_OPTS, ids=["default", "inverted_300"])
 def test_small_layout_against_staged_and_oracle(opts):
+    _small_layout_against_staged_and_oracle(opts, 48000)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("opts", VB_OPTS, ids=["default", "inverted_300"])
+def test_small_layout_against_staged_and_oracle_at_44k1(opts):
+    """the same at 44.1 kHz: other head, crossover bin, FIR length and crop"""
+    _small_layout_against_staged_and_oracle(opts, 44100)
+
+
+def _small_layout_against_staged_and_oracle(opts, fs):
     from oracle import estimator as oest
     spk_files = [["FL", "FR"], ["FC"]]
-    e, meas, layout, rs, firs = _setup(spk_files, M=2, seed=3)
+    e, meas, layout, rs, firs = _setup(spk_files, fs=fs, M=2, seed=3)
     rs.set_virtual_bass(**opts)
     got = _quiet(rs.run, meas)
     rows, res = rs.slice.results()
