@@ -1,7 +1,7 @@
 // Batched complex fp64 FFT whose sub-transforms live in LDS: one or two launches per transform instead of one launch per
 // radix pass through global memory.
 //
-//   N = P1 x P2 (each a product of the radices 8 / 4 / 2 / 3 / 5 / 11, each <= 1024):
+//   N = P1 x P2 (each a product of the radices 8 / 4 / 2 / 3 / 5 / 11, and 7 for the plans that ask for it, each <= 1024):
 //     pass 1   vectors = the P2 columns n2 (stride-P2 samples), P1-point transform over n1, x w_N^(n2 k1) -> Y[k1][n2]
 //     pass 2   vectors = the P1 rows k1 of Y (contiguous), P2-point transform over n2 -> X[k1 + P1 k2]
 //   N <= 1024: one pass, vectors = the transforms of the batch.
@@ -126,7 +126,7 @@ __device__ __forceinline__ void bf5(cplx* x) {
   x[3] = csub(m2, n2);
 }
 
-// generic R-point DFT with the R-th roots taken from the table (prime radices beyond 5: 11)
+// generic R-point DFT with the R-th roots taken from the table (prime radices beyond 5: 7, 11)
 template <int R, int DIR>
 __device__ __forceinline__ void bf_generic(cplx* x, const cplx* __restrict__ roots, int n_roots) {
   cplx w[R];
@@ -197,6 +197,7 @@ __device__ __forceinline__ void run_stages(const Args& a, cplx* buf, const cplx*
       case 2: stage<2, DIR, T>(buf, a.P, blk, tw_step, m, tw, a.roots, a.n_roots, tid); blk >>= 1; break;
       case 3: stage<3, DIR, T>(buf, a.P, blk, tw_step, m, tw, a.roots, a.n_roots, tid); blk /= 3; break;
       case 5: stage<5, DIR, T>(buf, a.P, blk, tw_step, m, tw, a.roots, a.n_roots, tid); blk /= 5; break;
+      case 7: stage<7, DIR, T>(buf, a.P, blk, tw_step, m, tw, a.roots, a.n_roots, tid); blk /= 7; break;
       case 11: stage<11, DIR, T>(buf, a.P, blk, tw_step, m, tw, a.roots, a.n_roots, tid); blk /= 11; break;
       default: break;
     }
@@ -309,28 +310,31 @@ struct Plan {
   bool ok = false;
 };
 
-inline bool factor_points(int P, std::vector<int>& radix) {
+// seven: also the radix 7 (scipy.fft.next_fast_len's lengths, K15); the plans of the other users are as they were
+inline bool factor_points(int P, std::vector<int>& radix, bool seven = false) {
   radix.clear();
   int n = P;
-  for (int r : {8, 4, 2, 3, 5, 11})
+  for (int r : {8, 4, 2, 3, 5, 7, 11}) {
+    if (r == 7 && !seven) continue;
     while (n % r == 0) {
       radix.push_back(r);
       n /= r;
     }
+  }
   return n == 1 && (int)radix.size() <= kMaxStages;
 }
 
 // N = P1 x P2 with both factors <= kMaxPoints, as balanced as the factors of N allow; P1 gets the larger one (the strided
 // pass then has more, shorter rows); every factor a product of the supported radices
-inline Plan make_plan(int N) {
+inline Plan make_plan(int N, bool seven = false) {
   Plan p;
   p.N = N;
   std::vector<int> tmp;
-  if (N < 2 || !factor_points(N, tmp) && N <= kMaxPoints) return p;
+  if (N < 2 || !factor_points(N, tmp, seven) && N <= kMaxPoints) return p;
   if (N <= kMaxPoints) {
     p.P1 = N;
     p.P2 = 1;
-    p.ok = factor_points(N, p.r1);
+    p.ok = factor_points(N, p.r1, seven);
     return p;
   }
   int best = 0;
@@ -339,13 +343,13 @@ inline Plan make_plan(int N) {
     const int b = N / a;
     if (b > kMaxPoints || b > a) continue;               // a >= b
     std::vector<int> ra, rb;
-    if (!factor_points(a, ra) || !factor_points(b, rb)) continue;
+    if (!factor_points(a, ra, seven) || !factor_points(b, rb, seven)) continue;
     if (best == 0 || a < best) best = a;                 // the most balanced split: smallest a with a >= b
   }
   if (!best) return p;
   p.P1 = best;
   p.P2 = N / best;
-  p.ok = factor_points(p.P1, p.r1) && factor_points(p.P2, p.r2);
+  p.ok = factor_points(p.P1, p.r1, seven) && factor_points(p.P2, p.r2, seven);
   return p;
 }
 

@@ -24,6 +24,7 @@
 #include "slice_kernels.hip.h"
 #include "vbass_kernels.hip.h"
 #include "micdev_kernels.hip.h"
+#include "analysis_kernels.hip.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -1824,6 +1825,259 @@ extern "C" int imp_mic_mismatch(imp_ctx* ctx, const double* x, const int64_t* of
   }
   rc = mic_mismatch_impl<double>(ctx, "imp_mic_mismatch", d_x, off, len, peak, group, side, anchor, B, G, win, pre, fs, grid, M,
                                  raw_out, power_out);
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)ctx_block_put(ctx, d_x);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// K15 binaural analysis metrics: band cross-spectra and IACF per speaker pair, energy decay curves per row
+// ------------------------------------------------------------------------------------------------
+// the arguments both metric entries share; *extent = elements the rows span
+static int binaural_check(const char* who, const void* x, const int64_t* off, const int64_t* len, int64_t P, const int64_t* nfft,
+                          const int64_t* bins, int64_t bands, int64_t D, const double* band_out, const double* iacf_out,
+                          const int64_t* peak_out, const double* energy_out, int64_t* extent) {
+  if (!off || !len || !iacf_out || !peak_out || !energy_out || (bands > 0 && (!nfft || !bins || !band_out)))
+    return fail(IMP_ERR_INVALID, "%s: null argument", who);
+  if (P < 1 || P > 65535) return fail(IMP_ERR_INVALID, "%s: P = %lld pairs (need 1 .. 65535)", who, (long long)P);
+  if (bands < 0 || bands > 65535) return fail(IMP_ERR_INVALID, "%s: %lld bands (need 0 .. 65535)", who, (long long)bands);
+  if (D < 0) return fail(IMP_ERR_INVALID, "%s: negative maximum lag %lld", who, (long long)D);
+  if (D > imp::kIacfMaxD)
+    return fail(IMP_ERR_UNSUPPORTED, "%s: maximum lag of %lld samples is above the limit of %d (10 ms at 192 kHz is 1920)", who,
+                (long long)D, imp::kIacfMaxD);
+  int64_t ext = 0;
+  for (int64_t r = 0; r < 2 * P; ++r) {
+    if (off[r] < 0 || len[r] < 0) return fail(IMP_ERR_INVALID, "%s: negative offset/length in row %lld", who, (long long)r);
+    if (len[r] > ((int64_t)1 << 22)) return fail(IMP_ERR_UNSUPPORTED, "%s: row %lld has %lld samples (limit 2^22)", who, (long long)r, (long long)len[r]);
+    ext = std::max<int64_t>(ext, off[r] + len[r]);
+  }
+  for (int64_t p = 0; bands > 0 && p < P; ++p) {
+    const int64_t n = nfft[p];
+    if (n < 1 || n > ((int64_t)1 << 22) || n < len[2 * p] || n < len[2 * p + 1])
+      return fail(IMP_ERR_INVALID, "%s: nfft = %lld of pair %lld (need 1 .. 2^22 and at least both rows' lengths %lld, %lld)", who,
+                  (long long)n, (long long)p, (long long)len[2 * p], (long long)len[2 * p + 1]);
+    int64_t r = n;
+    for (int64_t q : {2, 3, 5, 7, 11})
+      while (r % q == 0) r /= q;
+    if (r != 1) return fail(IMP_ERR_UNSUPPORTED, "%s: nfft = %lld of pair %lld is not 2^a 3^b 5^c 7^d 11^e", who, (long long)n, (long long)p);
+    for (int64_t b = 0; b < bands; ++b) {
+      const int64_t k0 = bins[(p * bands + b) * 2], k1 = bins[(p * bands + b) * 2 + 1];
+      if (k0 < 0 || k1 < k0 || k1 > n / 2 + 1)
+        return fail(IMP_ERR_INVALID, "%s: bins [%lld, %lld) of pair %lld, band %lld (need 0 <= k0 <= k1 <= nfft / 2 + 1 = %lld)", who,
+                    (long long)k0, (long long)k1, (long long)p, (long long)b, (long long)(n / 2 + 1));
+    }
+  }
+  if (ext > 0 && !x) return fail(IMP_ERR_INVALID, "%s: null rows", who);
+  *extent = ext;
+  return IMP_OK;
+}
+
+template <class T>
+static int binaural_metrics_impl(imp_ctx* ctx, const char* who, const T* d_x, const int64_t* off, const int64_t* len, int64_t P,
+                                 const int64_t* nfft, const int64_t* bins, int64_t bands, int64_t D, double* band_out,
+                                 double* iacf_out, int64_t* peak_out, double* energy_out) {
+  const int64_t nlag = 2 * D + 1;
+  // pairs in the order the spectra are taken: grouped by nfft (a std::map: ascending), call order inside a group
+  std::map<int64_t, std::vector<int64_t>> by_nfft;
+  int64_t tiles_pitch = 1;
+  std::vector<imp::AnPair> pairs((size_t)P);
+  for (int64_t p = 0; p < P; ++p) {
+    pairs[(size_t)p] = {off[2 * p], len[2 * p], off[2 * p + 1], len[2 * p + 1]};
+    tiles_pitch = std::max<int64_t>(tiles_pitch, (std::max(len[2 * p], len[2 * p + 1]) + imp::kIacfTile - 1) / imp::kIacfTile);
+    if (bands > 0) by_nfft[nfft[p]].push_back(p);
+  }
+  // at most 128 MiB per transform buffer: longer groups go through in chunks
+  struct Chunk { int64_t nfft, first, count; };
+  std::vector<Chunk> chunks;
+  std::vector<int64_t> order;                                          // pair of sorted position
+  size_t z_elems = 1;
+  for (auto& kv : by_nfft) {
+    const int64_t cap = std::max<int64_t>(1, ((int64_t)128 << 20) / (kv.first * (int64_t)sizeof(double2)));
+    for (size_t i = 0; i < kv.second.size(); i += (size_t)cap) {
+      const int64_t count = std::min<int64_t>(cap, (int64_t)(kv.second.size() - i));
+      chunks.push_back({kv.first, (int64_t)order.size(), count});
+      for (int64_t k = 0; k < count; ++k) order.push_back(kv.second[i + (size_t)k]);
+      z_elems = std::max(z_elems, (size_t)count * (size_t)kv.first);
+    }
+  }
+  // staged tables: pairs in call order | pairs in sorted order | bins in sorted order
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t pairs_b = up((size_t)P * sizeof(imp::AnPair));
+  const size_t bins_b = up(std::max<size_t>((size_t)P * (size_t)bands * 2, 1) * sizeof(long long));
+  char *h_tab = nullptr, *d_tab = nullptr;
+  int rc = ctx_stage(ctx, 2 * pairs_b + bins_b, (void**)&h_tab, (void**)&d_tab);
+  if (rc) return rc;
+  std::memcpy(h_tab, pairs.data(), (size_t)P * sizeof(imp::AnPair));
+  for (size_t i = 0; i < order.size(); ++i) {
+    const int64_t p = order[i];
+    reinterpret_cast<imp::AnPair*>(h_tab + pairs_b)[i] = pairs[(size_t)p];
+    for (int64_t q = 0; q < bands * 2; ++q)
+      reinterpret_cast<long long*>(h_tab + 2 * pairs_b)[(int64_t)i * bands * 2 + q] = (long long)bins[p * bands * 2 + q];
+  }
+  if ((rc = ctx_stage_push(ctx, h_tab, d_tab, 2 * pairs_b + bins_b))) return rc;
+  const imp::AnPair* d_pairs = (const imp::AnPair*)d_tab;
+  const imp::AnPair* d_sorted = (const imp::AnPair*)(d_tab + pairs_b);
+  const long long* d_bins = (const long long*)(d_tab + 2 * pairs_b);
+  // work: part [P][tiles_pitch][nlag + 2] | iacf [P][nlag] | energy [P][2] | peak [P] | band sums [P][bands][4] (sorted order)
+  const size_t part_n = (size_t)P * (size_t)tiles_pitch * (size_t)(nlag + 2), iacf_n = (size_t)P * (size_t)nlag;
+  const size_t band_n = (size_t)P * (size_t)bands * 4;
+  double* d_work = nullptr;
+  double2 *za = nullptr, *zb = nullptr;
+  hipStream_t s = ctx->stream;
+  auto cleanup = [&](int code) {
+    (void)hipStreamSynchronize(s);
+    (void)ctx_block_put(ctx, d_work);
+    (void)ctx_block_put(ctx, za);
+    (void)ctx_block_put(ctx, zb);
+    return code;
+  };
+  if ((rc = ctx_block_get(ctx, (part_n + iacf_n + 3 * (size_t)P + band_n + 1) * sizeof(double), (void**)&d_work))) return cleanup(rc);
+  double *d_part = d_work, *d_iacf = d_part + part_n, *d_energy = d_iacf + iacf_n;
+  long long* d_peak = reinterpret_cast<long long*>(d_energy + 2 * (size_t)P);
+  double* d_band = d_energy + 3 * (size_t)P;
+  if (bands > 0) {
+    if ((rc = ctx_block_get(ctx, z_elems * sizeof(double2), (void**)&za))) return cleanup(rc);
+    if ((rc = ctx_block_get(ctx, z_elems * sizeof(double2), (void**)&zb))) return cleanup(rc);
+  }
+  hipLaunchKernelGGL(imp::iacf_kernel<T>, dim3((unsigned)tiles_pitch, (unsigned)P), dim3(imp::kAnThreads), 0, s, d_x, d_pairs, (int)D,
+                     (long long)tiles_pitch, d_part);
+  if (hipGetLastError() != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "%s: IACF launch failed", who));
+  hipLaunchKernelGGL(imp::iacf_finish_kernel, dim3((unsigned)P), dim3(imp::kAnThreads), 0, s, d_pairs, (int)D, (long long)tiles_pitch,
+                     (const double*)d_part, d_iacf, d_peak, d_energy);
+  if (hipGetLastError() != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "%s: IACF reduction launch failed", who));
+  for (const Chunk& c : chunks) {
+    double2* z = nullptr;
+    if ((rc = analysis_pair_spectra(ctx, d_x, d_sorted + c.first, c.count, c.nfft, za, zb, &z))) return cleanup(rc);
+    hipLaunchKernelGGL(imp::band_cross_kernel, dim3((unsigned)bands, (unsigned)c.count), dim3(imp::kAnThreads), 0, s, (const double2*)z,
+                       (long long)c.nfft, d_bins + c.first * bands * 2, (int)bands, d_band + c.first * bands * 4);
+    if (hipGetLastError() != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "%s: band sums launch failed", who));
+  }
+  std::vector<double> h_band(band_n);
+  hipError_t e = hipMemcpyAsync(iacf_out, d_iacf, iacf_n * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(energy_out, d_energy, 2 * (size_t)P * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(peak_out, d_peak, (size_t)P * sizeof(long long), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && band_n) e = hipMemcpyAsync(h_band.data(), d_band, band_n * sizeof(double), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  if (e != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e)));
+  if (e2 != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e2)));
+  for (size_t i = 0; i < order.size(); ++i)
+    std::memcpy(band_out + order[i] * bands * 4, h_band.data() + i * (size_t)bands * 4, (size_t)bands * 4 * sizeof(double));
+  return cleanup(IMP_OK);
+}
+
+extern "C" int imp_binaural_metrics_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t P,
+                                           const int64_t* nfft, const int64_t* bins, int64_t bands, int64_t D, double* band_out,
+                                           double* iacf_out, int64_t* peak_out, double* energy_out) {
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_binaural_metrics_device: null ctx");
+  IMP_CTX_LOCK(ctx);
+  int64_t ext = 0;
+  int rc = binaural_check("imp_binaural_metrics_device", d_x, off, len, P, nfft, bins, bands, D, band_out, iacf_out, peak_out,
+                          energy_out, &ext);
+  if (rc || (rc = ctx_bind(ctx))) return rc;
+  return binaural_metrics_impl<float>(ctx, "imp_binaural_metrics_device", d_x, off, len, P, nfft, bins, bands, D, band_out, iacf_out,
+                                      peak_out, energy_out);
+}
+
+// fp64 host rows: uploaded as they are, then the same kernels on Sample = double
+static int upload_rows64(imp_ctx* ctx, const char* who, const double* x, int64_t ext, double** d_x) {
+  int rc = ctx_block_get(ctx, (size_t)std::max<int64_t>(ext, 1) * sizeof(double), (void**)d_x);
+  if (rc) return rc;
+  if (ext > 0) {
+    hipError_t e = hipMemcpyAsync(*d_x, x, (size_t)ext * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(ctx->stream);
+      (void)ctx_block_put(ctx, *d_x);
+      *d_x = nullptr;
+      return fail(IMP_ERR_HIP, "%s: h2d: %s", who, hipGetErrorString(e));
+    }
+  }
+  return IMP_OK;
+}
+
+extern "C" int imp_binaural_metrics(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t P,
+                                    const int64_t* nfft, const int64_t* bins, int64_t bands, int64_t D, double* band_out,
+                                    double* iacf_out, int64_t* peak_out, double* energy_out) {
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_binaural_metrics: null ctx");
+  IMP_CTX_LOCK(ctx);
+  int64_t ext = 0;
+  int rc = binaural_check("imp_binaural_metrics", x, off, len, P, nfft, bins, bands, D, band_out, iacf_out, peak_out, energy_out, &ext);
+  if (rc || (rc = ctx_bind(ctx))) return rc;
+  double* d_x = nullptr;
+  if ((rc = upload_rows64(ctx, "imp_binaural_metrics", x, ext, &d_x))) return rc;
+  rc = binaural_metrics_impl<double>(ctx, "imp_binaural_metrics", d_x, off, len, P, nfft, bins, bands, D, band_out, iacf_out, peak_out,
+                                     energy_out);
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)ctx_block_put(ctx, d_x);
+  return rc;
+}
+
+static int edc_check(const char* who, const void* x, const int64_t* off, const int64_t* len, int64_t B, double floor_db,
+                     const double* out, int64_t* extent, int64_t* total) {
+  if (!off || !len) return fail(IMP_ERR_INVALID, "%s: null argument", who);
+  if (B < 1 || B > 65535) return fail(IMP_ERR_INVALID, "%s: B = %lld rows (need 1 .. 65535)", who, (long long)B);
+  if (std::isnan(floor_db)) return fail(IMP_ERR_INVALID, "%s: floor_db is NaN", who);
+  int64_t ext = 0, tot = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "%s: negative offset/length in row %lld", who, (long long)b);
+    if (len[b] > ((int64_t)1 << 26)) return fail(IMP_ERR_UNSUPPORTED, "%s: row %lld has %lld samples (limit 2^26)", who, (long long)b, (long long)len[b]);
+    ext = std::max<int64_t>(ext, off[b] + len[b]);
+    tot += len[b];
+  }
+  if (ext > 0 && (!x || !out)) return fail(IMP_ERR_INVALID, "%s: null rows or output", who);
+  *extent = ext;
+  *total = tot;
+  return IMP_OK;
+}
+
+template <class T>
+static int edc_impl(imp_ctx* ctx, const char* who, const T* d_x, const int64_t* off, const int64_t* len, int64_t B, double floor_db,
+                    int64_t total, double* out) {
+  if (total == 0) return IMP_OK;
+  long long *h_tab = nullptr, *d_tab = nullptr;
+  int rc = ctx_stage(ctx, 3 * (size_t)B * sizeof(long long), (void**)&h_tab, (void**)&d_tab);
+  if (rc) return rc;
+  int64_t pos = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    h_tab[b] = off[b];
+    h_tab[B + b] = len[b];
+    h_tab[2 * B + b] = pos;
+    pos += len[b];
+  }
+  if ((rc = ctx_stage_push(ctx, h_tab, d_tab, 3 * (size_t)B * sizeof(long long)))) return rc;
+  double* d_work = nullptr;                                            // scan [total] | curves [total]
+  if ((rc = ctx_block_get(ctx, 2 * (size_t)total * sizeof(double), (void**)&d_work))) return rc;
+  hipStream_t s = ctx->stream;
+  hipLaunchKernelGGL(imp::edc_kernel<T>, dim3((unsigned)B), dim3(imp::kDecayThreads), 0, s, d_x, (const long long*)d_tab,
+                     (const long long*)(d_tab + B), (const long long*)(d_tab + 2 * B), floor_db, d_work, d_work + total);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_work + total, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  (void)ctx_block_put(ctx, d_work);
+  if (e != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+  if (e2 != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e2));
+  return IMP_OK;
+}
+
+extern "C" int imp_energy_decay_db_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t B,
+                                          double floor_db, double* out) {
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_energy_decay_db_device: null ctx");
+  IMP_CTX_LOCK(ctx);
+  int64_t ext = 0, total = 0;
+  int rc = edc_check("imp_energy_decay_db_device", d_x, off, len, B, floor_db, out, &ext, &total);
+  if (rc || (rc = ctx_bind(ctx))) return rc;
+  return edc_impl<float>(ctx, "imp_energy_decay_db_device", d_x, off, len, B, floor_db, total, out);
+}
+
+extern "C" int imp_energy_decay_db(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t B, double floor_db,
+                                   double* out) {
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_energy_decay_db: null ctx");
+  IMP_CTX_LOCK(ctx);
+  int64_t ext = 0, total = 0;
+  int rc = edc_check("imp_energy_decay_db", x, off, len, B, floor_db, out, &ext, &total);
+  if (rc || (rc = ctx_bind(ctx))) return rc;
+  double* d_x = nullptr;
+  if ((rc = upload_rows64(ctx, "imp_energy_decay_db", x, ext, &d_x))) return rc;
+  rc = edc_impl<double>(ctx, "imp_energy_decay_db", d_x, off, len, B, floor_db, total, out);
   (void)hipStreamSynchronize(ctx->stream);
   (void)ctx_block_put(ctx, d_x);
   return rc;

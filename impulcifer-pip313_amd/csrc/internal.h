@@ -112,3 +112,11 @@ void slice_norm_destroy(SliceNorm* p);
 int64_t slice_norm_mfft(const SliceNorm* p);
 int slice_norm_run(imp_ctx* ctx, SliceNorm* p, const float* d_rows, int64_t pitch, int rows_per_meas, const long long* d_n,
                    int64_t M, double* d_peak_db);
+
+// K15 (a) (minphase.hip, next to the fp64 transform): spectra of count pairs z = x_L + i x_R zero padded to nfft; a, b:
+// [count][nfft] work buffers, *z the one that holds the result; stream ordered, no wait
+namespace imp { struct AnPair; }
+int analysis_pair_spectra(imp_ctx* ctx, const float* d_x, const imp::AnPair* d_pairs, int64_t count, int64_t nfft, double2* a,
+                          double2* b, double2** z);
+int analysis_pair_spectra(imp_ctx* ctx, const double* d_x, const imp::AnPair* d_pairs, int64_t count, int64_t nfft, double2* a,
+                          double2* b, double2** z);

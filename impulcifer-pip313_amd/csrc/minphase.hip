@@ -26,6 +26,8 @@
 
 #include "internal.h"
 #include "fft64.hip.h"
+#define IMP_ANALYSIS_PAIR_HOOK_ONLY
+#include "analysis_kernels.hip.h"
 
 typedef double2 cdbl;
 
@@ -399,6 +401,7 @@ static int run_fft_passes(imp_ctx* ctx, const std::vector<int>& fac, const cdbl*
       case 2: hipLaunchKernelGGL(stockham_pass<2>, grid, block, 0, ctx->stream, *cur, *other, roots, N, n, s, dir); break;
       case 3: hipLaunchKernelGGL(stockham_pass<3>, grid, block, 0, ctx->stream, *cur, *other, roots, N, n, s, dir); break;
       case 5: hipLaunchKernelGGL(stockham_pass<5>, grid, block, 0, ctx->stream, *cur, *other, roots, N, n, s, dir); break;
+      case 7: hipLaunchKernelGGL(stockham_pass<7>, grid, block, 0, ctx->stream, *cur, *other, roots, N, n, s, dir); break;
       case 11: hipLaunchKernelGGL(stockham_pass<11>, grid, block, 0, ctx->stream, *cur, *other, roots, N, n, s, dir); break;
       default: return fail(IMP_ERR_UNSUPPORTED, "radix %d", r);
     }
@@ -450,8 +453,8 @@ static bool fft64_wanted() {
 // that the kernels between two transforms need no launch and no pass over memory of their own).
 template <class InOp, class OutOp>
 static int run_fft_ops(imp_ctx* ctx, const std::vector<int>& fac, const cdbl* roots, int N, int64_t B, int dir, cdbl** cur,
-                       cdbl** other, InOp in_op, OutOp out_op, bool* used_tiles = nullptr, int64_t in_pitch = 0) {
-  const fft64::Plan pl = fft64_wanted() ? fft64::make_plan(N) : fft64::Plan();
+                       cdbl** other, InOp in_op, OutOp out_op, bool* used_tiles = nullptr, int64_t in_pitch = 0, bool seven = false) {
+  const fft64::Plan pl = fft64_wanted() ? fft64::make_plan(N, seven) : fft64::Plan();
   if (used_tiles) *used_tiles = pl.ok;
   if (!pl.ok) return run_fft_passes(ctx, fac, roots, N, B, dir, cur, other);
   fft64::Args a = {};
@@ -1301,4 +1304,60 @@ int spectrum_pair_device(imp_ctx* ctx, const double* filter, int64_t M, int64_t 
                      reinterpret_cast<float2*>(d_hs), (int)Nc, N1);
   if (hipGetLastError() != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "pair spectrum launch failed"));
   return cleanup(IMP_OK);
+}
+
+// K15 (a): Z[p] = FFT_nfft(x_L + i x_R) of `count` pairs (analysis_kernels.hip.h), 11-smooth nfft as scipy.fft.next_fast_len
+// gives it (the factor 7 included).  a, b: [count][nfft] each; *z: whichever of them holds the result.  The tile transform
+// forms z in its load hook; lengths it does not hold go through plain radix passes after pair_pack_kernel, which also
+// serves nfft = 1.  Nothing here waits.
+template <class T>
+static int analysis_pair_spectra_t(imp_ctx* ctx, const T* d_x, const imp::AnPair* d_pairs, int64_t count, int64_t nfft, cdbl* a,
+                                   cdbl* b, cdbl** z) {
+  hipStream_t s = ctx->stream;
+  auto pack = [&]() {
+    hipLaunchKernelGGL(imp::pair_pack_kernel<T>, dim3((unsigned)((nfft + imp::kAnThreads - 1) / imp::kAnThreads), (unsigned)count),
+                       dim3(imp::kAnThreads), 0, s, d_x, d_pairs, a, (long long)nfft);
+    return hipGetLastError();
+  };
+  *z = a;
+  if (nfft == 1) {
+    HIP_TRY(pack());
+    return IMP_OK;
+  }
+  std::vector<int> fac;                                               // factorise() with the radix 7
+  {
+    int n = (int)nfft;
+    for (int r : {8, 4, 2, 3, 5, 7, 11})
+      while (n % r == 0) {
+        fac.push_back(r);
+        n /= r;
+      }
+    if (n != 1) return fail(IMP_ERR_UNSUPPORTED, "transform length %lld is not 2^a 3^b 5^c 7^d 11^e", (long long)nfft);
+  }
+  cdbl* roots = nullptr;
+  auto it = ctx->fft_roots.find((long long)nfft);
+  if (it != ctx->fft_roots.end()) {
+    roots = (cdbl*)it->second;
+  } else {
+    HIP_TRY(hipMalloc((void**)&roots, (size_t)nfft * sizeof(cdbl)));
+    hipLaunchKernelGGL(roots_kernel, dim3((unsigned)((nfft + 255) / 256)), dim3(256), 0, s, roots, (int)nfft);
+    HIP_TRY(hipGetLastError());
+    ctx->fft_roots[(long long)nfft] = roots;
+  }
+  cdbl *cur = a, *oth = b;
+  const bool tiles = fft64_wanted() && fft64::make_plan((int)nfft, true).ok;
+  if (!tiles) HIP_TRY(pack());
+  int rc = run_fft_ops(ctx, fac, roots, (int)nfft, count, -1, &cur, &oth, imp::PairIn<T>{d_x, d_pairs}, fft64::NoOp{}, nullptr, 0, true);
+  if (rc) return rc;
+  *z = cur;
+  return IMP_OK;
+}
+
+int analysis_pair_spectra(imp_ctx* ctx, const float* d_x, const imp::AnPair* d_pairs, int64_t count, int64_t nfft, double2* a,
+                          double2* b, double2** z) {
+  return analysis_pair_spectra_t<float>(ctx, d_x, d_pairs, count, nfft, a, b, z);
+}
+int analysis_pair_spectra(imp_ctx* ctx, const double* d_x, const imp::AnPair* d_pairs, int64_t count, int64_t nfft, double2* a,
+                          double2* b, double2** z) {
+  return analysis_pair_spectra_t<double>(ctx, d_x, d_pairs, count, nfft, a, b, z);
 }

@@ -188,6 +188,10 @@ SIGNATURES = {
                                           _i64, _i64, C.c_double, _pd, _i64, _pd, _pd]),
     "imp_mic_mismatch": (C.c_int, [_vp, _pd, _pi64, _pi64, _pi64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i64, _i64, _i64, _i64,
                                    C.c_double, _pd, _i64, _pd, _pd]),
+    "imp_binaural_metrics_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, _pi64, _pi64, _i64, _i64, _pd, _pd, _pi64, _pd]),
+    "imp_binaural_metrics": (C.c_int, [_vp, _pd, _pi64, _pi64, _i64, _pi64, _pi64, _i64, _i64, _pd, _pd, _pi64, _pd]),
+    "imp_energy_decay_db_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, C.c_double, _pd]),
+    "imp_energy_decay_db": (C.c_int, [_vp, _pd, _pi64, _pi64, _i64, C.c_double, _pd]),
     "imp_apply_window": (C.c_int, [_vp, _pf, _pi64, _pi64, _i64, C.POINTER(WindowParams)]),
     "imp_apply_window_device": (C.c_int, [_vp, _vp, _pi64, _vp, _pi64, _pi64, _i64, C.POINTER(WindowParams)]),
     "imp_segset_create_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, C.POINTER(_vp), _pd]),
@@ -389,6 +393,59 @@ class Context:
             _check(self._lib.imp_mic_mismatch_device(self._h, _vp(int(dptr)), _ptr_i64(offs), _ptr_i64(lens), _ptr_i64(peaks),
                                                      *p32, *tail))
         return raw, power
+
+    @staticmethod
+    def _pack_rows64(rows):
+        rows = [np.asarray(r, dtype=np.float64).ravel() for r in rows]
+        lens = np.array([len(r) for r in rows], dtype=np.int64)
+        offs = np.zeros(len(rows), dtype=np.int64)
+        if len(rows):
+            offs[1:] = np.cumsum(lens)[:-1]
+        flat = np.ascontiguousarray(np.concatenate(rows) if int(lens.sum()) else np.zeros(1), dtype=np.float64)
+        return flat, offs, lens
+
+    def binaural_metrics(self, rows, nfft, bins, D, dptr=None):
+        """K15 (imp_binaural_metrics / imp_binaural_metrics_device) for P pairs, rows in the order left, right, left, ...:
+        (band sums [P, bands, 4], iacf [P, 2 D + 1], peak index [P], energies [P, 2]).  bins: [P, bands, 2] bin ranges of
+        the nfft[p]-point spectra.  rows: host 1-D arrays (fp64 upload), or with dptr the (offsets, lengths) of fp32 device
+        rows at dptr."""
+        nfft = np.ascontiguousarray(nfft, dtype=np.int64)
+        P = len(nfft)
+        bins = np.ascontiguousarray(bins, dtype=np.int64).reshape(P, -1, 2)
+        bands = bins.shape[1]
+        D = int(D)
+        band = np.zeros((P, bands, 4), dtype=np.float64)
+        iacf = np.zeros((P, 2 * max(D, 0) + 1), dtype=np.float64)
+        peak = np.zeros(P, dtype=np.int64)
+        energy = np.zeros((P, 2), dtype=np.float64)
+        tail = (P, _ptr_i64(nfft), _ptr_i64(bins), bands, D, band.ctypes.data_as(_pd), iacf.ctypes.data_as(_pd), _ptr_i64(peak),
+                energy.ctypes.data_as(_pd))
+        if dptr is None:
+            flat, offs, lens = self._pack_rows64(rows)
+            _check(self._lib.imp_binaural_metrics(self._h, flat.ctypes.data_as(_pd), _ptr_i64(offs), _ptr_i64(lens), *tail))
+        else:
+            offs = np.ascontiguousarray(rows[0], dtype=np.int64)
+            lens = np.ascontiguousarray(rows[1], dtype=np.int64)
+            _check(self._lib.imp_binaural_metrics_device(self._h, _vp(int(dptr)), _ptr_i64(offs), _ptr_i64(lens), *tail))
+        return band, iacf, peak, energy
+
+    def energy_decay_db(self, rows, floor_db=-80.0, dptr=None):
+        """K15 (imp_energy_decay_db / imp_energy_decay_db_device): the energy decay curve of every row, a list of fp64 arrays.
+        rows as in binaural_metrics."""
+        if dptr is None:
+            flat, offs, lens = self._pack_rows64(rows)
+        else:
+            offs = np.ascontiguousarray(rows[0], dtype=np.int64)
+            lens = np.ascontiguousarray(rows[1], dtype=np.int64)
+        out = np.zeros(max(int(lens.sum()), 1), dtype=np.float64)
+        if dptr is None:
+            _check(self._lib.imp_energy_decay_db(self._h, flat.ctypes.data_as(_pd), _ptr_i64(offs), _ptr_i64(lens), len(lens),
+                                                 float(floor_db), out.ctypes.data_as(_pd)))
+        else:
+            _check(self._lib.imp_energy_decay_db_device(self._h, _vp(int(dptr)), _ptr_i64(offs), _ptr_i64(lens), len(lens),
+                                                        float(floor_db), out.ctypes.data_as(_pd)))
+        ends = np.cumsum(lens)
+        return [out[int(e - n):int(e)].copy() for e, n in zip(ends, lens)]
 
     # ---- device-resident rows (fp32 at dptr + off[b], len[b] samples) ---------------------------
     @staticmethod

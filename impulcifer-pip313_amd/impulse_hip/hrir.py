@@ -430,6 +430,23 @@ class HRIR(object):
                            "late_db": 20 * np.log10(rms_late / rms_direct + epsilon)}
         return out
 
+    def binaural_analysis(self, bands=None, max_delay_ms=1.0, edc=False):
+        """ILD, IPD, IACC and (with edc) the energy decay curves of every speaker that has both ears, in self.irs order: what
+        the reference's HRIRPlotter.generate_{ild,ipd,iacc,etc}_bokeh_layout compute before they draw (hrir_plotter.py:574-860
+        with the functions analysis.py restates).  {speaker: {"bands", "ild_db", "ipd_deg", "iacc", "tau_ms", "lags_ms", "iacf"[,
+        "edc_db": {side: curve}]}}.  One K15 call for all pairs (analysis.binaural_metrics); rows that live on the device
+        are read there and stay there."""
+        from .analysis import binaural_metrics
+        speakers = [sp for sp, pair in self.irs.items() if "left" in pair and "right" in pair]
+        res = binaural_metrics([(self.irs[sp]["left"], self.irs[sp]["right"]) for sp in speakers], self.fs, bands=bands,
+                               max_delay_ms=max_delay_ms, edc=edc)
+        out = {}
+        for sp, r in zip(speakers, res):
+            out[sp] = {k: r[k] for k in ("bands", "ild_db", "ipd_deg", "iacc", "tau_ms", "lags_ms", "iacf")}
+            if edc:
+                out[sp]["edc_db"] = {"left": r["edc_db"][0], "right": r["edc_db"][1]}
+        return out
+
     # ---- cropping ------------------------------------------------------------------------
     def _all_irs(self):
         return [(sp, sd, ir) for sp, pair in self.irs.items() for sd, ir in pair.items()]

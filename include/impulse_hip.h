@@ -373,6 +373,37 @@ int imp_mic_mismatch(imp_ctx* ctx, const double* x, const int64_t* off, const in
                      const int32_t* group, const int32_t* side, const int32_t* anchor, int64_t B, int64_t G, int64_t win,
                      int64_t pre, double fs, const double* grid, int64_t M, double* raw_out, double* power_out);
 
+/* ---- K15: binaural analysis metrics of finished rows, fp64 ------------------------------------------
+ * The numerical core of the reference's binaural plots, core/plotting/analysis.py, as HRIRPlotter calls it on the rows of
+ * every speaker pair (core/plotting/hrir_plotter.py:574-860: generate_ild / ipd / iacc / etc_bokeh_layout).
+ * Rows 2p and 2p + 1 are the left and the right ear of pair p (P pairs; lengths may differ and may be 0).
+ *   band sums (:31-58 _band_cross_spectra): band_out[p][b] = (sum |L[k]|^2, sum |R[k]|^2, re and im of sum L[k] conj R[k])
+ *     over the bins bins[p][b] = (k0, k1), k0 <= k < k1, of the nfft[p]-point spectra.  nfft[p] is
+ *     scipy.fft.next_fast_len(max(len)) (2^a 3^b 5^c 7^d 11^e, at least both lengths, at most 2^22); the bin ranges are the
+ *     caller's evaluation of the reference's (fftfreq >= f_low) & (fftfreq < min(f_high, fs / 2)): 0 <= k0 <= k1 <= nfft / 2 + 1,
+ *     an empty range gives four NaN.  bands = 0 skips this part (nfft, bins, band_out may then be NULL).
+ *   IACF (:103-138 interaural_cross_correlation): iacf_out[p][j] = sum_n l[n + j - D] r[n] / sqrt(sum l^2 sum r^2) for the
+ *     2 D + 1 lags -D .. D (scipy.signal.correlate(l, r, 'full') with correlation_lags); D = round(max_delay_ms fs / 1000) is
+ *     the caller's, at most 2048 (IMP_ERR_UNSUPPORTED above: 10 ms at 192 kHz is 1920).  peak_out[p]: the first j of
+ *     max |iacf| among the lags 'full' mode has, -(len_r - 1) <= j - D <= len_l - 1 (-1 if there is none);
+ *     energy_out[p] = (sum l^2, sum r^2): the caller returns the reference's empty result when their product is <= 0.
+ * A pair's results do not depend on the other pairs of the call.  Synchronous.
+ * imp_binaural_metrics_device: fp32 device rows at d_x + off[r];  imp_binaural_metrics: fp64 host rows at x + off[r]. */
+int imp_binaural_metrics_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t P,
+                                const int64_t* nfft, const int64_t* bins, int64_t bands, int64_t D, double* band_out,
+                                double* iacf_out, int64_t* peak_out, double* energy_out);
+int imp_binaural_metrics(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t P, const int64_t* nfft,
+                         const int64_t* bins, int64_t bands, int64_t D, double* band_out, double* iacf_out, int64_t* peak_out,
+                         double* energy_out);
+/* core/plotting/analysis.py:90-100 energy_decay_curve_db (hrir_plotter.py generate_etc_bokeh_layout): per row the Schroeder
+ * integral e[i] = sum_{j >= i} x[j]^2 as 10 log10(e / (e[0] + 1e-12) + 1e-12), or floor_db everywhere when e[0] <= 1e-12.
+ * out: the B curves packed one after the other at the rows' own lengths (sum of len values).  Synchronous.
+ * imp_energy_decay_db_device: fp32 device rows at d_x + off[b];  imp_energy_decay_db: fp64 host rows at x + off[b]. */
+int imp_energy_decay_db_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t B, double floor_db,
+                               double* out);
+int imp_energy_decay_db(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t B, double floor_db,
+                        double* out);
+
 /* ---- K6: minimum-phase FIR design, batched, fp64 -----------------------------------------------
  * Tail of FrequencyResponse.minimum_phase_impulse_response (autoeq/frequency_response.py:676-680),
  * called per channel by core/parallel_workers.py:129:
