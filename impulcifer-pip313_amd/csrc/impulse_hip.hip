@@ -8,13 +8,16 @@
 #include <cmath>
 #include <complex>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "internal.h"
@@ -155,6 +158,89 @@ int ctx_stage(imp_ctx* ctx, size_t bytes, void** host, void** dev) {
 }
 int ctx_stage_push(imp_ctx* ctx, const void* host, void* dev, size_t bytes) {
   HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  return IMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ragged rows: a base pointer plus off[B] / len[B].  What the entry points of the analysis stages share: the check of
+// the row table, the way of small tables to the device, and the pooled block that holds uploaded rows for a call
+// ------------------------------------------------------------------------------------------------
+struct RowSpan {
+  int64_t extent = 0, total = 0, maxlen = 0;      // max(off + len), sum of len, longest row
+};
+static constexpr int64_t kAnyLen = INT64_MAX;     // rows_check: no limit on a row's length
+
+// the row table of `who`: refused when B < 0, a table is missing, an entry is negative or a row is longer than max_len
+static int rows_check(const char* who, const int64_t* off, const int64_t* len, int64_t B, int64_t max_len, RowSpan* out) {
+  *out = RowSpan();
+  if (B < 0) return fail(IMP_ERR_INVALID, "%s: B < 0", who);
+  if (B > 0 && (!off || !len)) return fail(IMP_ERR_INVALID, "%s: null row table", who);
+  for (int64_t b = 0; b < B; ++b) {
+    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "%s: negative offset/length in row %lld", who, (long long)b);
+    if (len[b] > max_len)
+      return fail(IMP_ERR_UNSUPPORTED, "%s: row %lld has %lld samples (limit %lld)", who, (long long)b, (long long)len[b],
+                  (long long)max_len);
+    out->extent = std::max(out->extent, off[b] + len[b]);
+    out->total += len[b];
+    out->maxlen = std::max(out->maxlen, len[b]);
+  }
+  return IMP_OK;
+}
+
+// N host tables through the staging ring: laid out 8-byte aligned in ONE allocation and sent with ONE copy in stream
+// order; dev[i] = where piece i lies on the device (valid as ctx_stage says)
+struct TablePiece {
+  const void* host;
+  size_t bytes;
+};
+template <size_t N>
+static int ctx_stage_tables(imp_ctx* ctx, const TablePiece (&piece)[N], void* (&dev)[N]) {
+  size_t at[N], bytes = 0;
+  for (size_t i = 0; i < N; ++i) {
+    at[i] = bytes;
+    bytes += (piece[i].bytes + 7) & ~(size_t)7;
+  }
+  bytes = std::max<size_t>(bytes, 8);
+  char *h = nullptr, *d = nullptr;
+  int rc = ctx_stage(ctx, bytes, (void**)&h, (void**)&d);
+  if (rc) return rc;
+  for (size_t i = 0; i < N; ++i) {
+    if (piece[i].bytes) std::memcpy(h + at[i], piece[i].host, piece[i].bytes);
+    dev[i] = d + at[i];
+  }
+  return ctx_stage_push(ctx, h, d, bytes);
+}
+
+// A pooled block for the length of a call: whichever way the call ends, the stream is drained and the block handed back.
+// release(): the block lives on with a new owner (a segment set).
+struct BlockHold {
+  imp_ctx* ctx;
+  void* p = nullptr;
+  explicit BlockHold(imp_ctx* c) : ctx(c) {}
+  BlockHold(const BlockHold&) = delete;
+  BlockHold& operator=(const BlockHold&) = delete;
+  ~BlockHold() {
+    if (!p) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)ctx_block_put(ctx, p);
+  }
+  int get(size_t bytes) { return ctx_block_get(ctx, bytes, &p); }
+  void* release() {
+    void* q = p;
+    p = nullptr;
+    return q;
+  }
+};
+
+// host rows x[0, extent) into a pooled block, as they are (the kernels read Sample = T)
+template <class T>
+static int upload_rows(imp_ctx* ctx, const char* who, const T* x, int64_t extent, BlockHold& rows) {
+  int rc = rows.get((size_t)std::max<int64_t>(extent, 1) * sizeof(T));
+  if (rc) return rc;
+  if (extent > 0) {
+    const hipError_t e = hipMemcpyAsync(rows.p, x, (size_t)extent * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return fail(IMP_ERR_HIP, "%s: h2d: %s", who, hipGetErrorString(e));
+  }
   return IMP_OK;
 }
 
@@ -1512,15 +1598,13 @@ extern "C" int imp_plan_debug_run_stage(imp_plan* p, const float* x, int64_t B, 
 // ------------------------------------------------------------------------------------------------
 // K3 peak index, K4/K8 windows (ragged batches)
 // ------------------------------------------------------------------------------------------------
-static int peak_index_impl(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t B,
+static int peak_index_impl(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t B, int64_t maxlen,
                            double peak_height, int64_t* idx_out, float* maxabs_out) {
   // the search works on |x| against one positive threshold (the reference's callers pass 0.12589 = -18 dB)
   if (!(peak_height > 0.0)) return fail(IMP_ERR_INVALID, "peak_height must be positive (got %g)", peak_height);
   if (B == 0) return IMP_OK;
-  int64_t maxlen = 0;
-  for (int64_t b = 0; b < B; ++b) maxlen = std::max(maxlen, len[b]);
   const int64_t chunks = std::max<int64_t>(1, (maxlen + imp::kPeakChunk - 1) / imp::kPeakChunk);
-  // scratch: off[B], len[B], res[B] (RowPeak), chunk maxima [B][chunks]
+  // scratch: res[B] (RowPeak), chunk maxima [B][chunks]; off[B], len[B] through the staging ring
   const size_t meta = (size_t)B * sizeof(int64_t);
   const size_t res_bytes = (size_t)B * sizeof(imp::RowPeak);
   void* scr = nullptr;
@@ -1529,12 +1613,9 @@ static int peak_index_impl(imp_ctx* ctx, const float* d_x, const int64_t* off, c
   imp::RowPeak* d_res = (imp::RowPeak*)scr;
   unsigned* d_chunk = (unsigned*)(d_res + B);
   hipStream_t s = ctx->stream;
-  int64_t *h_tab = nullptr, *d_off = nullptr;
-  if ((rc = ctx_stage(ctx, 2 * meta, (void**)&h_tab, (void**)&d_off))) return rc;
-  int64_t* d_len = d_off + B;
-  std::memcpy(h_tab, off, meta);
-  std::memcpy(h_tab + B, len, meta);
-  if ((rc = ctx_stage_push(ctx, h_tab, d_off, 2 * meta))) return rc;
+  void* tab[2];
+  if ((rc = ctx_stage_tables(ctx, {{off, meta}, {len, meta}}, tab))) return rc;
+  const int64_t *d_off = (const int64_t*)tab[0], *d_len = (const int64_t*)tab[1];
   hipLaunchKernelGGL(imp::row_chunk_max_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, d_x, d_off, d_len,
                      (int64_t)0, d_chunk, chunks);
   HIP_TRY(hipGetLastError());
@@ -1559,43 +1640,27 @@ static int peak_index_impl(imp_ctx* ctx, const float* d_x, const int64_t* off, c
 
 extern "C" int imp_peak_index_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len,
                                      int64_t B, double peak_height, int64_t* idx_out, float* maxabs_out) {
-  if (!ctx || (B && (!d_x || !off || !len || !idx_out))) return fail(IMP_ERR_INVALID, "imp_peak_index_device: null argument");
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_peak_index_device: null ctx");
   IMP_CTX_LOCK(ctx);
-  if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
-  for (int64_t b = 0; b < B; ++b)
-    if (len[b] < 0 || off[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in row %lld", (long long)b);
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
-  return peak_index_impl(ctx, d_x, off, len, B, peak_height, idx_out, maxabs_out);
+  if (B && (!d_x || !idx_out)) return fail(IMP_ERR_INVALID, "imp_peak_index_device: null argument");
+  RowSpan sp;
+  int rc = rows_check("imp_peak_index_device", off, len, B, kAnyLen, &sp);
+  if (rc || (rc = ctx_bind(ctx))) return rc;
+  return peak_index_impl(ctx, d_x, off, len, B, sp.maxlen, peak_height, idx_out, maxabs_out);
 }
 
 extern "C" int imp_peak_index(imp_ctx* ctx, const float* x, const int64_t* off, const int64_t* len, int64_t B,
                               double peak_height, int64_t* idx_out, float* maxabs_out) {
-  if (!ctx || (B && (!x || !off || !len || !idx_out))) return fail(IMP_ERR_INVALID, "imp_peak_index: null argument");
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_peak_index: null ctx");
   IMP_CTX_LOCK(ctx);
-  if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
-  if (B == 0) return IMP_OK;
-  int64_t total = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    if (len[b] < 0 || off[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in row %lld", (long long)b);
-    total = std::max(total, off[b] + len[b]);
-  }
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
-  float* d_x = nullptr;
-  if (total > 0) {
-    if ((rc = ctx_block_get(ctx, (size_t)total * sizeof(float), (void**)&d_x))) return rc;
-    hipError_t e = hipMemcpyAsync(d_x, x, (size_t)total * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)ctx_block_put(ctx, d_x);
-      return fail(IMP_ERR_HIP, "h2d: %s", hipGetErrorString(e));
-    }
-  }
-  rc = peak_index_impl(ctx, d_x, off, len, B, peak_height, idx_out, maxabs_out);
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)ctx_block_put(ctx, d_x);
-  return rc;
+  if (B && (!x || !idx_out)) return fail(IMP_ERR_INVALID, "imp_peak_index: null argument");
+  RowSpan sp;
+  int rc = rows_check("imp_peak_index", off, len, B, kAnyLen, &sp);
+  if (rc || B == 0) return rc;
+  if ((rc = ctx_bind(ctx))) return rc;
+  BlockHold rows(ctx);
+  if ((rc = upload_rows(ctx, "imp_peak_index", x, sp.extent, rows))) return rc;
+  return peak_index_impl(ctx, (const float*)rows.p, off, len, B, sp.maxlen, peak_height, idx_out, maxabs_out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1731,9 +1796,9 @@ static int mic_mismatch_impl(imp_ctx* ctx, const char* who, const T* d_x, const 
   const imp::MicInterp* d_interp = (const imp::MicInterp*)(d_tab + rows_b + bins_b);
   // work: mag [B][pitch] | power [B][M] | raw [G][M]
   const size_t mag_n = (size_t)B * (size_t)pitch, pow_n = (size_t)B * (size_t)M, raw_n = (size_t)G * (size_t)M;
-  double* d_work = nullptr;
-  if ((rc = ctx_block_get(ctx, (mag_n + pow_n + raw_n) * sizeof(double), (void**)&d_work))) return rc;
-  double *d_mag = d_work, *d_pow = d_work + mag_n, *d_raw = d_pow + pow_n;
+  BlockHold work(ctx);
+  if ((rc = work.get((mag_n + pow_n + raw_n) * sizeof(double)))) return rc;
+  double *d_mag = (double*)work.p, *d_pow = d_mag + mag_n, *d_raw = d_pow + pow_n;
   hipStream_t s = ctx->stream;
   const unsigned mblocks = (unsigned)((M + imp::kMicThreads - 1) / imp::kMicThreads);
   hipError_t e = hipSuccess;
@@ -1755,16 +1820,15 @@ static int mic_mismatch_impl(imp_ctx* ctx, const char* who, const T* d_x, const 
   if (e == hipSuccess) e = hipMemcpyAsync(raw_out, d_raw, raw_n * sizeof(double), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && power_out) e = hipMemcpyAsync(power_out, d_pow, pow_n * sizeof(double), hipMemcpyDeviceToHost, s);
   const hipError_t e2 = hipStreamSynchronize(s);
-  (void)ctx_block_put(ctx, d_work);
   if (e != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   if (e2 != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e2));
   return IMP_OK;
 }
 
-// the arguments both entries share, refused with the reason; *extent = elements the rows span (max off + len)
+// the arguments both entries share, refused with the reason; *sp = what the rows span
 static int mic_check(const char* who, const void* x, const int64_t* off, const int64_t* len, const int64_t* peak,
                      const int32_t* group, const int32_t* side, const int32_t* anchor, int64_t B, int64_t G, int64_t win,
-                     int64_t pre, double fs, const double* grid, int64_t M, const double* raw_out, int64_t* extent) {
+                     int64_t pre, double fs, const double* grid, int64_t M, const double* raw_out, RowSpan* sp) {
   if (!off || !len || !peak || !group || !side || !anchor || !grid || !raw_out)
     return fail(IMP_ERR_INVALID, "%s: null argument", who);
   if (B < 2 || G < 1 || G > 65535 || B > 65535) return fail(IMP_ERR_INVALID, "%s: B = %lld rows in G = %lld groups (need 2 <= B, 1 <= G, both <= 65535)", who, (long long)B, (long long)G);
@@ -1775,20 +1839,18 @@ static int mic_check(const char* who, const void* x, const int64_t* off, const i
   for (int64_t g = 0; g < M; ++g)
     if (!std::isfinite(grid[g]) || !(grid[g] > 0.0) || (g && !(grid[g] > grid[g - 1])))
       return fail(IMP_ERR_INVALID, "%s: grid must be positive, finite and increasing (point %lld)", who, (long long)g);
+  int rc = rows_check(who, off, len, B, kAnyLen, sp);
+  if (rc) return rc;
   std::vector<int> seen((size_t)G * 2, 0);
-  int64_t ext = 0;
   for (int64_t b = 0; b < B; ++b) {
-    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "%s: negative offset/length in row %lld", who, (long long)b);
     if (group[b] < 0 || group[b] >= G) return fail(IMP_ERR_INVALID, "%s: row %lld names group %d of %lld", who, (long long)b, group[b], (long long)G);
     if (side[b] != 0 && side[b] != 1) return fail(IMP_ERR_INVALID, "%s: row %lld has side %d (0 left, 1 right)", who, (long long)b, side[b]);
     if (anchor[b]) seen[(size_t)group[b] * 2 + side[b]] = 1;
-    ext = std::max<int64_t>(ext, off[b] + len[b]);
   }
   for (int64_t g = 0; g < G; ++g)
     if (!seen[(size_t)g * 2] || !seen[(size_t)g * 2 + 1])
       return fail(IMP_ERR_INVALID, "%s: group %lld has no anchor row for the %s ear", who, (long long)g, seen[(size_t)g * 2] ? "right" : "left");
-  if (ext > 0 && !x) return fail(IMP_ERR_INVALID, "%s: null rows", who);
-  *extent = ext;
+  if (sp->extent > 0 && !x) return fail(IMP_ERR_INVALID, "%s: null rows", who);
   return IMP_OK;
 }
 
@@ -1798,45 +1860,35 @@ extern "C" int imp_mic_mismatch_device(imp_ctx* ctx, const float* d_x, const int
                                        double* power_out) {
   if (!ctx) return fail(IMP_ERR_INVALID, "imp_mic_mismatch_device: null ctx");
   IMP_CTX_LOCK(ctx);
-  int64_t ext = 0;
-  int rc = mic_check("imp_mic_mismatch_device", d_x, off, len, peak, group, side, anchor, B, G, win, pre, fs, grid, M, raw_out, &ext);
+  RowSpan sp;
+  int rc = mic_check("imp_mic_mismatch_device", d_x, off, len, peak, group, side, anchor, B, G, win, pre, fs, grid, M, raw_out, &sp);
   if (rc || (rc = ctx_bind(ctx))) return rc;
   return mic_mismatch_impl<float>(ctx, "imp_mic_mismatch_device", d_x, off, len, peak, group, side, anchor, B, G, win, pre, fs, grid,
                                   M, raw_out, power_out);
 }
 
+// fp64 host rows: uploaded as they are, then the same kernels on Sample = double
 extern "C" int imp_mic_mismatch(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, const int64_t* peak,
                                 const int32_t* group, const int32_t* side, const int32_t* anchor, int64_t B, int64_t G, int64_t win,
                                 int64_t pre, double fs, const double* grid, int64_t M, double* raw_out, double* power_out) {
   if (!ctx) return fail(IMP_ERR_INVALID, "imp_mic_mismatch: null ctx");
   IMP_CTX_LOCK(ctx);
-  int64_t ext = 0;
-  int rc = mic_check("imp_mic_mismatch", x, off, len, peak, group, side, anchor, B, G, win, pre, fs, grid, M, raw_out, &ext);
+  RowSpan sp;
+  int rc = mic_check("imp_mic_mismatch", x, off, len, peak, group, side, anchor, B, G, win, pre, fs, grid, M, raw_out, &sp);
   if (rc || (rc = ctx_bind(ctx))) return rc;
-  double* d_x = nullptr;
-  if ((rc = ctx_block_get(ctx, (size_t)std::max<int64_t>(ext, 1) * sizeof(double), (void**)&d_x))) return rc;
-  if (ext > 0) {
-    hipError_t e = hipMemcpyAsync(d_x, x, (size_t)ext * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)ctx_block_put(ctx, d_x);
-      return fail(IMP_ERR_HIP, "imp_mic_mismatch: h2d: %s", hipGetErrorString(e));
-    }
-  }
-  rc = mic_mismatch_impl<double>(ctx, "imp_mic_mismatch", d_x, off, len, peak, group, side, anchor, B, G, win, pre, fs, grid, M,
-                                 raw_out, power_out);
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)ctx_block_put(ctx, d_x);
-  return rc;
+  BlockHold rows(ctx);
+  if ((rc = upload_rows(ctx, "imp_mic_mismatch", x, sp.extent, rows))) return rc;
+  return mic_mismatch_impl<double>(ctx, "imp_mic_mismatch", (const double*)rows.p, off, len, peak, group, side, anchor, B, G, win, pre,
+                                   fs, grid, M, raw_out, power_out);
 }
 
 // ------------------------------------------------------------------------------------------------
 // K15 binaural analysis metrics: band cross-spectra and IACF per speaker pair, energy decay curves per row
 // ------------------------------------------------------------------------------------------------
-// the arguments both metric entries share; *extent = elements the rows span
+// the arguments both metric entries share; *sp = what the rows span
 static int binaural_check(const char* who, const void* x, const int64_t* off, const int64_t* len, int64_t P, const int64_t* nfft,
                           const int64_t* bins, int64_t bands, int64_t D, const double* band_out, const double* iacf_out,
-                          const int64_t* peak_out, const double* energy_out, int64_t* extent) {
+                          const int64_t* peak_out, const double* energy_out, RowSpan* sp) {
   if (!off || !len || !iacf_out || !peak_out || !energy_out || (bands > 0 && (!nfft || !bins || !band_out)))
     return fail(IMP_ERR_INVALID, "%s: null argument", who);
   if (P < 1 || P > 65535) return fail(IMP_ERR_INVALID, "%s: P = %lld pairs (need 1 .. 65535)", who, (long long)P);
@@ -1845,12 +1897,8 @@ static int binaural_check(const char* who, const void* x, const int64_t* off, co
   if (D > imp::kIacfMaxD)
     return fail(IMP_ERR_UNSUPPORTED, "%s: maximum lag of %lld samples is above the limit of %d (10 ms at 192 kHz is 1920)", who,
                 (long long)D, imp::kIacfMaxD);
-  int64_t ext = 0;
-  for (int64_t r = 0; r < 2 * P; ++r) {
-    if (off[r] < 0 || len[r] < 0) return fail(IMP_ERR_INVALID, "%s: negative offset/length in row %lld", who, (long long)r);
-    if (len[r] > ((int64_t)1 << 22)) return fail(IMP_ERR_UNSUPPORTED, "%s: row %lld has %lld samples (limit 2^22)", who, (long long)r, (long long)len[r]);
-    ext = std::max<int64_t>(ext, off[r] + len[r]);
-  }
+  int rc = rows_check(who, off, len, 2 * P, (int64_t)1 << 22, sp);
+  if (rc) return rc;
   for (int64_t p = 0; bands > 0 && p < P; ++p) {
     const int64_t n = nfft[p];
     if (n < 1 || n > ((int64_t)1 << 22) || n < len[2 * p] || n < len[2 * p + 1])
@@ -1867,8 +1915,7 @@ static int binaural_check(const char* who, const void* x, const int64_t* off, co
                     (long long)k0, (long long)k1, (long long)p, (long long)b, (long long)(n / 2 + 1));
     }
   }
-  if (ext > 0 && !x) return fail(IMP_ERR_INVALID, "%s: null rows", who);
-  *extent = ext;
+  if (sp->extent > 0 && !x) return fail(IMP_ERR_INVALID, "%s: null rows", who);
   return IMP_OK;
 }
 
@@ -1921,36 +1968,26 @@ static int binaural_metrics_impl(imp_ctx* ctx, const char* who, const T* d_x, co
   // work: part [P][tiles_pitch][nlag + 2] | iacf [P][nlag] | energy [P][2] | peak [P] | band sums [P][bands][4] (sorted order)
   const size_t part_n = (size_t)P * (size_t)tiles_pitch * (size_t)(nlag + 2), iacf_n = (size_t)P * (size_t)nlag;
   const size_t band_n = (size_t)P * (size_t)bands * 4;
-  double* d_work = nullptr;
-  double2 *za = nullptr, *zb = nullptr;
   hipStream_t s = ctx->stream;
-  auto cleanup = [&](int code) {
-    (void)hipStreamSynchronize(s);
-    (void)ctx_block_put(ctx, d_work);
-    (void)ctx_block_put(ctx, za);
-    (void)ctx_block_put(ctx, zb);
-    return code;
-  };
-  if ((rc = ctx_block_get(ctx, (part_n + iacf_n + 3 * (size_t)P + band_n + 1) * sizeof(double), (void**)&d_work))) return cleanup(rc);
-  double *d_part = d_work, *d_iacf = d_part + part_n, *d_energy = d_iacf + iacf_n;
+  BlockHold work(ctx), spec_a(ctx), spec_b(ctx);
+  if ((rc = work.get((part_n + iacf_n + 3 * (size_t)P + band_n + 1) * sizeof(double)))) return rc;
+  double *d_part = (double*)work.p, *d_iacf = d_part + part_n, *d_energy = d_iacf + iacf_n;
   long long* d_peak = reinterpret_cast<long long*>(d_energy + 2 * (size_t)P);
   double* d_band = d_energy + 3 * (size_t)P;
-  if (bands > 0) {
-    if ((rc = ctx_block_get(ctx, z_elems * sizeof(double2), (void**)&za))) return cleanup(rc);
-    if ((rc = ctx_block_get(ctx, z_elems * sizeof(double2), (void**)&zb))) return cleanup(rc);
-  }
+  if (bands > 0 && ((rc = spec_a.get(z_elems * sizeof(double2))) || (rc = spec_b.get(z_elems * sizeof(double2))))) return rc;
+  double2 *za = (double2*)spec_a.p, *zb = (double2*)spec_b.p;
   hipLaunchKernelGGL(imp::iacf_kernel<T>, dim3((unsigned)tiles_pitch, (unsigned)P), dim3(imp::kAnThreads), 0, s, d_x, d_pairs, (int)D,
                      (long long)tiles_pitch, d_part);
-  if (hipGetLastError() != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "%s: IACF launch failed", who));
+  if (hipGetLastError() != hipSuccess) return fail(IMP_ERR_HIP, "%s: IACF launch failed", who);
   hipLaunchKernelGGL(imp::iacf_finish_kernel, dim3((unsigned)P), dim3(imp::kAnThreads), 0, s, d_pairs, (int)D, (long long)tiles_pitch,
                      (const double*)d_part, d_iacf, d_peak, d_energy);
-  if (hipGetLastError() != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "%s: IACF reduction launch failed", who));
+  if (hipGetLastError() != hipSuccess) return fail(IMP_ERR_HIP, "%s: IACF reduction launch failed", who);
   for (const Chunk& c : chunks) {
     double2* z = nullptr;
-    if ((rc = analysis_pair_spectra(ctx, d_x, d_sorted + c.first, c.count, c.nfft, za, zb, &z))) return cleanup(rc);
+    if ((rc = analysis_pair_spectra(ctx, d_x, d_sorted + c.first, c.count, c.nfft, za, zb, &z))) return rc;
     hipLaunchKernelGGL(imp::band_cross_kernel, dim3((unsigned)bands, (unsigned)c.count), dim3(imp::kAnThreads), 0, s, (const double2*)z,
                        (long long)c.nfft, d_bins + c.first * bands * 2, (int)bands, d_band + c.first * bands * 4);
-    if (hipGetLastError() != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "%s: band sums launch failed", who));
+    if (hipGetLastError() != hipSuccess) return fail(IMP_ERR_HIP, "%s: band sums launch failed", who);
   }
   std::vector<double> h_band(band_n);
   hipError_t e = hipMemcpyAsync(iacf_out, d_iacf, iacf_n * sizeof(double), hipMemcpyDeviceToHost, s);
@@ -1958,11 +1995,11 @@ static int binaural_metrics_impl(imp_ctx* ctx, const char* who, const T* d_x, co
   if (e == hipSuccess) e = hipMemcpyAsync(peak_out, d_peak, (size_t)P * sizeof(long long), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && band_n) e = hipMemcpyAsync(h_band.data(), d_band, band_n * sizeof(double), hipMemcpyDeviceToHost, s);
   const hipError_t e2 = hipStreamSynchronize(s);
-  if (e != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e)));
-  if (e2 != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e2)));
+  if (e != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+  if (e2 != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e2));
   for (size_t i = 0; i < order.size(); ++i)
     std::memcpy(band_out + order[i] * bands * 4, h_band.data() + i * (size_t)bands * 4, (size_t)bands * 4 * sizeof(double));
-  return cleanup(IMP_OK);
+  return IMP_OK;
 }
 
 extern "C" int imp_binaural_metrics_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t P,
@@ -1970,62 +2007,37 @@ extern "C" int imp_binaural_metrics_device(imp_ctx* ctx, const float* d_x, const
                                            double* iacf_out, int64_t* peak_out, double* energy_out) {
   if (!ctx) return fail(IMP_ERR_INVALID, "imp_binaural_metrics_device: null ctx");
   IMP_CTX_LOCK(ctx);
-  int64_t ext = 0;
+  RowSpan sp;
   int rc = binaural_check("imp_binaural_metrics_device", d_x, off, len, P, nfft, bins, bands, D, band_out, iacf_out, peak_out,
-                          energy_out, &ext);
+                          energy_out, &sp);
   if (rc || (rc = ctx_bind(ctx))) return rc;
   return binaural_metrics_impl<float>(ctx, "imp_binaural_metrics_device", d_x, off, len, P, nfft, bins, bands, D, band_out, iacf_out,
                                       peak_out, energy_out);
 }
 
 // fp64 host rows: uploaded as they are, then the same kernels on Sample = double
-static int upload_rows64(imp_ctx* ctx, const char* who, const double* x, int64_t ext, double** d_x) {
-  int rc = ctx_block_get(ctx, (size_t)std::max<int64_t>(ext, 1) * sizeof(double), (void**)d_x);
-  if (rc) return rc;
-  if (ext > 0) {
-    hipError_t e = hipMemcpyAsync(*d_x, x, (size_t)ext * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)ctx_block_put(ctx, *d_x);
-      *d_x = nullptr;
-      return fail(IMP_ERR_HIP, "%s: h2d: %s", who, hipGetErrorString(e));
-    }
-  }
-  return IMP_OK;
-}
-
 extern "C" int imp_binaural_metrics(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t P,
                                     const int64_t* nfft, const int64_t* bins, int64_t bands, int64_t D, double* band_out,
                                     double* iacf_out, int64_t* peak_out, double* energy_out) {
   if (!ctx) return fail(IMP_ERR_INVALID, "imp_binaural_metrics: null ctx");
   IMP_CTX_LOCK(ctx);
-  int64_t ext = 0;
-  int rc = binaural_check("imp_binaural_metrics", x, off, len, P, nfft, bins, bands, D, band_out, iacf_out, peak_out, energy_out, &ext);
+  RowSpan sp;
+  int rc = binaural_check("imp_binaural_metrics", x, off, len, P, nfft, bins, bands, D, band_out, iacf_out, peak_out, energy_out, &sp);
   if (rc || (rc = ctx_bind(ctx))) return rc;
-  double* d_x = nullptr;
-  if ((rc = upload_rows64(ctx, "imp_binaural_metrics", x, ext, &d_x))) return rc;
-  rc = binaural_metrics_impl<double>(ctx, "imp_binaural_metrics", d_x, off, len, P, nfft, bins, bands, D, band_out, iacf_out, peak_out,
-                                     energy_out);
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)ctx_block_put(ctx, d_x);
-  return rc;
+  BlockHold rows(ctx);
+  if ((rc = upload_rows(ctx, "imp_binaural_metrics", x, sp.extent, rows))) return rc;
+  return binaural_metrics_impl<double>(ctx, "imp_binaural_metrics", (const double*)rows.p, off, len, P, nfft, bins, bands, D, band_out,
+                                       iacf_out, peak_out, energy_out);
 }
 
 static int edc_check(const char* who, const void* x, const int64_t* off, const int64_t* len, int64_t B, double floor_db,
-                     const double* out, int64_t* extent, int64_t* total) {
+                     const double* out, RowSpan* sp) {
   if (!off || !len) return fail(IMP_ERR_INVALID, "%s: null argument", who);
   if (B < 1 || B > 65535) return fail(IMP_ERR_INVALID, "%s: B = %lld rows (need 1 .. 65535)", who, (long long)B);
   if (std::isnan(floor_db)) return fail(IMP_ERR_INVALID, "%s: floor_db is NaN", who);
-  int64_t ext = 0, tot = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "%s: negative offset/length in row %lld", who, (long long)b);
-    if (len[b] > ((int64_t)1 << 26)) return fail(IMP_ERR_UNSUPPORTED, "%s: row %lld has %lld samples (limit 2^26)", who, (long long)b, (long long)len[b]);
-    ext = std::max<int64_t>(ext, off[b] + len[b]);
-    tot += len[b];
-  }
-  if (ext > 0 && (!x || !out)) return fail(IMP_ERR_INVALID, "%s: null rows or output", who);
-  *extent = ext;
-  *total = tot;
+  int rc = rows_check(who, off, len, B, (int64_t)1 << 26, sp);
+  if (rc) return rc;
+  if (sp->extent > 0 && (!x || !out)) return fail(IMP_ERR_INVALID, "%s: null rows or output", who);
   return IMP_OK;
 }
 
@@ -2033,26 +2045,24 @@ template <class T>
 static int edc_impl(imp_ctx* ctx, const char* who, const T* d_x, const int64_t* off, const int64_t* len, int64_t B, double floor_db,
                     int64_t total, double* out) {
   if (total == 0) return IMP_OK;
-  long long *h_tab = nullptr, *d_tab = nullptr;
-  int rc = ctx_stage(ctx, 3 * (size_t)B * sizeof(long long), (void**)&h_tab, (void**)&d_tab);
-  if (rc) return rc;
-  int64_t pos = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    h_tab[b] = off[b];
-    h_tab[B + b] = len[b];
-    h_tab[2 * B + b] = pos;
-    pos += len[b];
+  std::vector<int64_t> pos((size_t)B);                                 // where row b's curve starts in out
+  for (int64_t b = 0, at = 0; b < B; ++b) {
+    pos[(size_t)b] = at;
+    at += len[b];
   }
-  if ((rc = ctx_stage_push(ctx, h_tab, d_tab, 3 * (size_t)B * sizeof(long long)))) return rc;
-  double* d_work = nullptr;                                            // scan [total] | curves [total]
-  if ((rc = ctx_block_get(ctx, 2 * (size_t)total * sizeof(double), (void**)&d_work))) return rc;
+  const size_t meta = (size_t)B * sizeof(int64_t);
+  void* tab[3];
+  int rc = ctx_stage_tables(ctx, {{off, meta}, {len, meta}, {pos.data(), meta}}, tab);
+  if (rc) return rc;
+  BlockHold work(ctx);                                                 // scan [total] | curves [total]
+  if ((rc = work.get(2 * (size_t)total * sizeof(double)))) return rc;
+  double* d_work = (double*)work.p;
   hipStream_t s = ctx->stream;
-  hipLaunchKernelGGL(imp::edc_kernel<T>, dim3((unsigned)B), dim3(imp::kDecayThreads), 0, s, d_x, (const long long*)d_tab,
-                     (const long long*)(d_tab + B), (const long long*)(d_tab + 2 * B), floor_db, d_work, d_work + total);
+  hipLaunchKernelGGL(imp::edc_kernel<T>, dim3((unsigned)B), dim3(imp::kDecayThreads), 0, s, d_x, (const long long*)tab[0],
+                     (const long long*)tab[1], (const long long*)tab[2], floor_db, d_work, d_work + total);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_work + total, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, s);
   const hipError_t e2 = hipStreamSynchronize(s);
-  (void)ctx_block_put(ctx, d_work);
   if (e != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   if (e2 != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e2));
   return IMP_OK;
@@ -2062,25 +2072,22 @@ extern "C" int imp_energy_decay_db_device(imp_ctx* ctx, const float* d_x, const 
                                           double floor_db, double* out) {
   if (!ctx) return fail(IMP_ERR_INVALID, "imp_energy_decay_db_device: null ctx");
   IMP_CTX_LOCK(ctx);
-  int64_t ext = 0, total = 0;
-  int rc = edc_check("imp_energy_decay_db_device", d_x, off, len, B, floor_db, out, &ext, &total);
+  RowSpan sp;
+  int rc = edc_check("imp_energy_decay_db_device", d_x, off, len, B, floor_db, out, &sp);
   if (rc || (rc = ctx_bind(ctx))) return rc;
-  return edc_impl<float>(ctx, "imp_energy_decay_db_device", d_x, off, len, B, floor_db, total, out);
+  return edc_impl<float>(ctx, "imp_energy_decay_db_device", d_x, off, len, B, floor_db, sp.total, out);
 }
 
 extern "C" int imp_energy_decay_db(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t B, double floor_db,
                                    double* out) {
   if (!ctx) return fail(IMP_ERR_INVALID, "imp_energy_decay_db: null ctx");
   IMP_CTX_LOCK(ctx);
-  int64_t ext = 0, total = 0;
-  int rc = edc_check("imp_energy_decay_db", x, off, len, B, floor_db, out, &ext, &total);
+  RowSpan sp;
+  int rc = edc_check("imp_energy_decay_db", x, off, len, B, floor_db, out, &sp);
   if (rc || (rc = ctx_bind(ctx))) return rc;
-  double* d_x = nullptr;
-  if ((rc = upload_rows64(ctx, "imp_energy_decay_db", x, ext, &d_x))) return rc;
-  rc = edc_impl<double>(ctx, "imp_energy_decay_db", d_x, off, len, B, floor_db, total, out);
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)ctx_block_put(ctx, d_x);
-  return rc;
+  BlockHold rows(ctx);
+  if ((rc = upload_rows(ctx, "imp_energy_decay_db", x, sp.extent, rows))) return rc;
+  return edc_impl<double>(ctx, "imp_energy_decay_db", (const double*)rows.p, off, len, B, floor_db, sp.total, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2358,15 +2365,13 @@ struct imp_segset {
   imp_ctx* ctx = nullptr;
   int64_t B = 0;
   double* e = nullptr;               // squared, normalised segments, concatenated
-  int64_t* off = nullptr;            // device copies of the row table
+  int64_t* off = nullptr;            // device copies of the row table: one block of the set's own, they outlive the call
   int64_t* len = nullptr;
   std::vector<int64_t> h_len;
   void* qbuf = nullptr;              // query staging: 3 x int64 + 1 x double per query
   size_t qcap = 0;
-  // imp_segset_create_device without maxabs_out does not drain the stream: its staging lives as long as the set
+  // imp_segset_create_device without maxabs_out does not drain the stream: the row maxima live as long as the set
   void* keep_a = nullptr;
-  void* keep_b = nullptr;
-  std::vector<int64_t> keep_host;
 };
 
 extern "C" void imp_segset_destroy(imp_segset* s) {
@@ -2378,147 +2383,94 @@ extern "C" void imp_segset_destroy(imp_segset* s) {
   (void)ctx_block_put(s->ctx, s->off);
   (void)ctx_block_put(s->ctx, s->qbuf);
   (void)ctx_block_put(s->ctx, s->keep_a);
-  (void)ctx_block_put(s->ctx, s->keep_b);
   delete s;
+}
+
+// T = double: host segments, uploaded where they lie (the set keeps the caller's offsets).  T = float: fp32 rows on the
+// device, converted into a packed copy (offsets = running sum of the lengths); without maxabs_out that form returns
+// without waiting: the first imp_segset_range_means call waits for all of it.
+// The set's off | len go from the staging ring's pinned side straight into the set's block; only the source offsets of
+// the device form, which nothing reads after seg_from_float_kernel, lie in the ring's device side.
+template <class T>
+static int segset_create_impl(imp_ctx* ctx, const char* who, const T* x, const int64_t* off, const int64_t* len, int64_t B,
+                              imp_segset** out, double* maxabs_out) {
+  constexpr bool resident = std::is_same<T, float>::value;
+  if (!ctx) return fail(IMP_ERR_INVALID, "%s: null ctx", who);
+  IMP_CTX_LOCK(ctx);
+  if (!out || (B && !x)) return fail(IMP_ERR_INVALID, "%s: null argument", who);
+  *out = nullptr;
+  RowSpan sp;
+  int rc = rows_check(who, off, len, B, kAnyLen, &sp);
+  if (rc || (rc = ctx_bind(ctx))) return rc;
+  const int64_t total = resident ? sp.total : sp.extent;               // samples of s->e
+  std::unique_ptr<imp_segset> s(new (std::nothrow) imp_segset());
+  if (!s) return fail(IMP_ERR_ALLOC, "out of host memory");
+  s->ctx = ctx;
+  s->B = B;
+  s->h_len.assign(len, len + B);
+  hipStream_t st = ctx->stream;
+  BlockHold e(ctx), tab(ctx), mx(ctx);
+  if (e.get((size_t)std::max<int64_t>(total, 1) * sizeof(double)) || tab.get((size_t)std::max<int64_t>(2 * B, 1) * sizeof(int64_t)) ||
+      (B && mx.get((size_t)B * sizeof(unsigned long long))))
+    return fail(IMP_ERR_ALLOC, "%s: device allocation of %lld samples failed", who, (long long)total);
+  double* d_e = (double*)e.p;
+  int64_t *d_off = (int64_t*)tab.p, *d_len = d_off + B;
+  unsigned long long* d_max = (unsigned long long*)mx.p;
+  if (B == 0 || total == 0) {
+    if (maxabs_out)
+      for (int64_t b = 0; b < B; ++b) maxabs_out[b] = 0.0;
+    (void)ctx_block_put(ctx, mx.release());                            // nothing was queued: handed back without a wait
+  } else {
+    const size_t meta = (size_t)B * sizeof(int64_t);
+    int64_t *h_tab = nullptr, *d_tab = nullptr;                        // off of the set | len | off of the source rows
+    if ((rc = ctx_stage(ctx, 3 * meta, (void**)&h_tab, (void**)&d_tab))) return rc;
+    for (int64_t b = 0, at = 0; b < B; ++b) {
+      h_tab[b] = resident ? at : off[b];
+      h_tab[B + b] = len[b];
+      h_tab[2 * B + b] = off[b];
+      at += len[b];
+    }
+    if ((rc = ctx_stage_push(ctx, h_tab, d_off, 2 * meta))) return rc;
+    if (resident) {
+      if ((rc = ctx_stage_push(ctx, h_tab + 2 * B, d_tab + 2 * B, meta))) return rc;
+    } else if (hipMemcpyAsync(d_e, x, (size_t)total * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) {
+      return fail(IMP_ERR_HIP, "%s: upload failed", who);
+    }
+    if (hipMemsetAsync(d_max, 0, (size_t)B * sizeof(unsigned long long), st) != hipSuccess)
+      return fail(IMP_ERR_HIP, "%s: upload failed", who);
+    const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(256, (sp.maxlen + 4095) / 4096));
+    dim3 grid((unsigned)bpr, (unsigned)B), block(256);
+    if constexpr (resident)
+      hipLaunchKernelGGL(imp::seg_from_float_kernel, grid, block, 0, st, x, (const int64_t*)(d_tab + 2 * B), d_e, d_off, d_len);
+    hipLaunchKernelGGL(imp::seg_maxabs_kernel, grid, block, 0, st, d_e, d_off, d_len, d_max);
+    hipLaunchKernelGGL(imp::seg_square_kernel, grid, block, 0, st, d_e, d_off, d_len, d_max);
+    if (hipGetLastError() != hipSuccess) return fail(IMP_ERR_HIP, "%s: launch failed", who);
+    if (resident && !maxabs_out) {
+      s->keep_a = mx.release();                                        // stream ordered: no wait, the maxima go with the set
+    } else {
+      std::vector<unsigned long long> h((size_t)B);
+      if (hipMemcpyAsync(h.data(), d_max, (size_t)B * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess)
+        return fail(IMP_ERR_HIP, "%s: readback failed", who);
+      if (maxabs_out)
+        for (int64_t b = 0; b < B; ++b) std::memcpy(&maxabs_out[b], &h[(size_t)b], sizeof(double));
+    }
+  }
+  s->e = (double*)e.release();
+  s->off = (int64_t*)tab.release();
+  s->len = s->off + B;
+  *out = s.release();
+  return IMP_OK;
 }
 
 extern "C" int imp_segset_create(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t B,
                                  imp_segset** out, double* maxabs_out) {
-  if (!ctx || !out || (B && (!x || !off || !len))) return fail(IMP_ERR_INVALID, "imp_segset_create: null argument");
-  IMP_CTX_LOCK(ctx);
-  *out = nullptr;
-  if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
-  int64_t total = 0, maxlen = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in segment %lld", (long long)b);
-    total = std::max(total, off[b] + len[b]);
-    maxlen = std::max(maxlen, len[b]);
-  }
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
-  imp_segset* s = new (std::nothrow) imp_segset();
-  if (!s) return fail(IMP_ERR_ALLOC, "out of host memory");
-  s->ctx = ctx;
-  s->B = B;
-  s->h_len.assign(len, len + B);
-  hipStream_t st = ctx->stream;
-  unsigned long long* d_max = nullptr;
-  auto bail = [&](int code) {
-    (void)hipStreamSynchronize(st);
-    (void)ctx_block_put(ctx, d_max);
-    imp_segset_destroy(s);
-    return code;
-  };
-  if (ctx_block_get(ctx, (size_t)std::max<int64_t>(total, 1) * sizeof(double), (void**)&s->e) ||
-      ctx_block_get(ctx, (size_t)std::max<int64_t>(2 * B, 1) * sizeof(int64_t), (void**)&s->off) ||
-      ctx_block_get(ctx, (size_t)std::max<int64_t>(B, 1) * sizeof(unsigned long long), (void**)&d_max))
-    return bail(fail(IMP_ERR_ALLOC, "imp_segset_create: device allocation of %lld samples failed", (long long)total));
-  s->len = s->off + B;
-  if (B == 0 || total == 0) {
-    (void)ctx_block_put(ctx, d_max);
-    *out = s;
-    if (maxabs_out)
-      for (int64_t b = 0; b < B; ++b) maxabs_out[b] = 0.0;
-    return IMP_OK;
-  }
-  if (hipMemcpyAsync(s->e, x, (size_t)total * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(s->off, off, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(s->len, len, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemsetAsync(d_max, 0, (size_t)B * sizeof(unsigned long long), st) != hipSuccess)
-    return bail(fail(IMP_ERR_HIP, "imp_segset_create: upload failed"));
-  const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(256, (maxlen + 4095) / 4096));
-  dim3 grid((unsigned)bpr, (unsigned)B), block(256);
-  hipLaunchKernelGGL(imp::seg_maxabs_kernel, grid, block, 0, st, s->e, s->off, s->len, d_max);
-  hipLaunchKernelGGL(imp::seg_square_kernel, grid, block, 0, st, s->e, s->off, s->len, d_max);
-  if (hipGetLastError() != hipSuccess) return bail(fail(IMP_ERR_HIP, "imp_segset_create: launch failed"));
-  std::vector<unsigned long long> h((size_t)B);
-  if (hipMemcpyAsync(h.data(), d_max, (size_t)B * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return bail(fail(IMP_ERR_HIP, "imp_segset_create: readback failed"));
-  (void)ctx_block_put(ctx, d_max);
-  d_max = nullptr;
-  if (maxabs_out)
-    for (int64_t b = 0; b < B; ++b) std::memcpy(&maxabs_out[b], &h[(size_t)b], sizeof(double));
-  *out = s;
-  return IMP_OK;
+  return segset_create_impl<double>(ctx, "imp_segset_create", x, off, len, B, out, maxabs_out);
 }
 
 extern "C" int imp_segset_create_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t B,
                                         imp_segset** out, double* maxabs_out) {
-  if (!ctx || !out || (B && (!d_x || !off || !len))) return fail(IMP_ERR_INVALID, "imp_segset_create_device: null argument");
-  IMP_CTX_LOCK(ctx);
-  *out = nullptr;
-  if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
-  int64_t total = 0, maxlen = 0;
-  std::vector<int64_t> packed((size_t)std::max<int64_t>(B, 1));
-  for (int64_t b = 0; b < B; ++b) {
-    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in segment %lld", (long long)b);
-    packed[(size_t)b] = total;
-    total += len[b];
-    maxlen = std::max(maxlen, len[b]);
-  }
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
-  imp_segset* s = new (std::nothrow) imp_segset();
-  if (!s) return fail(IMP_ERR_ALLOC, "out of host memory");
-  s->ctx = ctx;
-  s->B = B;
-  s->h_len.assign(len, len + B);
-  hipStream_t st = ctx->stream;
-  unsigned long long* d_max = nullptr;
-  int64_t* d_src_off = nullptr;
-  auto bail = [&](int code) {
-    (void)hipStreamSynchronize(st);
-    (void)ctx_block_put(ctx, d_max);
-    (void)ctx_block_put(ctx, d_src_off);
-    imp_segset_destroy(s);
-    return code;
-  };
-  if (ctx_block_get(ctx, (size_t)std::max<int64_t>(total, 1) * sizeof(double), (void**)&s->e) ||
-      ctx_block_get(ctx, (size_t)std::max<int64_t>(2 * B, 1) * sizeof(int64_t), (void**)&s->off) ||
-      ctx_block_get(ctx, (size_t)std::max<int64_t>(B, 1) * sizeof(int64_t), (void**)&d_src_off) ||
-      ctx_block_get(ctx, (size_t)std::max<int64_t>(B, 1) * sizeof(unsigned long long), (void**)&d_max))
-    return bail(fail(IMP_ERR_ALLOC, "imp_segset_create_device: device allocation of %lld samples failed", (long long)total));
-  s->len = s->off + B;
-  if (B == 0 || total == 0) {
-    (void)ctx_block_put(ctx, d_max);
-    (void)ctx_block_put(ctx, d_src_off);
-    *out = s;
-    if (maxabs_out)
-      for (int64_t b = 0; b < B; ++b) maxabs_out[b] = 0.0;
-    return IMP_OK;
-  }
-  // the three small tables travel as ONE block (host copy kept by the set: without maxabs_out nothing below waits)
-  s->keep_host.resize((size_t)(3 * B));
-  std::copy(packed.begin(), packed.begin() + B, s->keep_host.begin());
-  std::copy(len, len + B, s->keep_host.begin() + B);
-  std::copy(off, off + B, s->keep_host.begin() + 2 * B);
-  if (hipMemcpyAsync(s->off, s->keep_host.data(), (size_t)(2 * B) * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d_src_off, s->keep_host.data() + 2 * B, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemsetAsync(d_max, 0, (size_t)B * sizeof(unsigned long long), st) != hipSuccess)
-    return bail(fail(IMP_ERR_HIP, "imp_segset_create_device: upload failed"));
-  const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(256, (maxlen + 4095) / 4096));
-  dim3 grid((unsigned)bpr, (unsigned)B), block(256);
-  hipLaunchKernelGGL(imp::seg_from_float_kernel, grid, block, 0, st, d_x, d_src_off, s->e, s->off, s->len);
-  hipLaunchKernelGGL(imp::seg_maxabs_kernel, grid, block, 0, st, s->e, s->off, s->len, d_max);
-  hipLaunchKernelGGL(imp::seg_square_kernel, grid, block, 0, st, s->e, s->off, s->len, d_max);
-  if (hipGetLastError() != hipSuccess) return bail(fail(IMP_ERR_HIP, "imp_segset_create_device: launch failed"));
-  if (!maxabs_out) {
-    // stream-ordered: the first imp_segset_range_means call waits for all of it; the staging goes with the set
-    s->keep_a = d_max;
-    s->keep_b = d_src_off;
-    *out = s;
-    return IMP_OK;
-  }
-  std::vector<unsigned long long> h((size_t)B);
-  if (hipMemcpyAsync(h.data(), d_max, (size_t)B * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return bail(fail(IMP_ERR_HIP, "imp_segset_create_device: readback failed"));
-  (void)ctx_block_put(ctx, d_max);
-  (void)ctx_block_put(ctx, d_src_off);
-  for (int64_t b = 0; b < B; ++b) std::memcpy(&maxabs_out[b], &h[(size_t)b], sizeof(double));
-  *out = s;
-  return IMP_OK;
+  return segset_create_impl<float>(ctx, "imp_segset_create_device", d_x, off, len, B, out, maxabs_out);
 }
 
 extern "C" int imp_segset_range_means(imp_segset* s, const int64_t* q_seg, const int64_t* q_a, const int64_t* q_b,
@@ -2568,37 +2520,32 @@ extern "C" int imp_segset_range_means(imp_segset* s, const int64_t* q_seg, const
 extern "C" int imp_decay_knees_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t B,
                                       double fs, double peak_height, int64_t* peak_out, int64_t* knee_out,
                                       double* floor_out, int64_t* window_out, int32_t* flags_out) {
-  if (!ctx || (B && (!d_x || !off || !len || !peak_out || !knee_out || !floor_out || !window_out || !flags_out)))
-    return fail(IMP_ERR_INVALID, "imp_decay_knees_device: null argument");
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_decay_knees_device: null ctx");
   IMP_CTX_LOCK(ctx);
-  if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
+  if (B && (!d_x || !peak_out || !knee_out || !floor_out || !window_out || !flags_out))
+    return fail(IMP_ERR_INVALID, "imp_decay_knees_device: null argument");
+  RowSpan sp;
+  int rc = rows_check("imp_decay_knees_device", off, len, B, kAnyLen, &sp);
+  if (rc) return rc;
   if (!(fs > 0.0) || !(fs < 1e9)) return fail(IMP_ERR_INVALID, "imp_decay_knees_device: fs must be positive (got %g)", fs);
   if (!(peak_height > 0.0)) return fail(IMP_ERR_INVALID, "peak_height must be positive (got %g)", peak_height);
   if (B == 0) return IMP_OK;
-  int64_t maxlen = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    if (len[b] < 0 || off[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in row %lld", (long long)b);
+  for (int64_t b = 0; b < B; ++b)
     if (len[b] >= ((int64_t)1 << 31)) return fail(IMP_ERR_INVALID, "row %lld is too long (%lld samples)", (long long)b, (long long)len[b]);
-    maxlen = std::max(maxlen, len[b]);
-  }
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
+  if ((rc = ctx_bind(ctx))) return rc;
+  const int64_t maxlen = sp.maxlen;
   const int64_t two_fs = (int64_t)(2 * fs);               // int(2 * fs), core/decay.py:84
   const int64_t span_max = std::max<int64_t>(1, std::min(two_fs, maxlen));
   const int64_t chunks = std::max<int64_t>(1, (maxlen + imp::kPeakChunk - 1) / imp::kPeakChunk);
   const int mean_pitch = imp::kKneeMaxWindows + 1;
   // scratch: span maxima bits [B] | peak results [B] | search state [B] | window means [B][mean_pitch] | chunk maxima
-  // [B][chunks].  The spans are read where they are (fp32 rows): no fp64 copy of them is made.
+  // [B][chunks]; off[B], len[B] through the staging ring.  The spans are read where they are (fp32 rows): no fp64 copy
+  // of them is made.
   const size_t meta = (size_t)B * sizeof(int64_t);
   size_t bytes = (size_t)B * sizeof(unsigned long long) + (size_t)B * sizeof(imp::RowPeak) + (size_t)B * sizeof(imp::KneeRow) +
                  (size_t)B * mean_pitch * sizeof(double) + (size_t)(B * chunks) * sizeof(unsigned);
   void* scr = nullptr;
   if ((rc = ctx_scratch(ctx, bytes, &scr))) return rc;
-  int64_t *h_tab = nullptr, *d_off = nullptr;
-  if ((rc = ctx_stage(ctx, 2 * meta, (void**)&h_tab, (void**)&d_off))) return rc;
-  int64_t* d_len = d_off + B;
-  std::memcpy(h_tab, off, meta);
-  std::memcpy(h_tab + B, len, meta);
   unsigned long long* d_max = (unsigned long long*)scr;
   imp::RowPeak* d_res = (imp::RowPeak*)(d_max + B);
   imp::KneeRow* d_rows = (imp::KneeRow*)(d_res + B);
@@ -2606,7 +2553,9 @@ extern "C" int imp_decay_knees_device(imp_ctx* ctx, const float* d_x, const int6
   unsigned* d_chunk = (unsigned*)(d_means + (size_t)B * mean_pitch);
   hipStream_t s = ctx->stream;
   std::vector<imp::KneeRow> h((size_t)B);
-  if ((rc = ctx_stage_push(ctx, h_tab, d_off, 2 * meta))) return rc;
+  void* tab[2];
+  if ((rc = ctx_stage_tables(ctx, {{off, meta}, {len, meta}}, tab))) return rc;
+  const int64_t *d_off = (const int64_t*)tab[0], *d_len = (const int64_t*)tab[1];
   hipLaunchKernelGGL(imp::row_chunk_max_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, d_x, d_off, d_len,
                      (int64_t)0, d_chunk, chunks);
   hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)B), dim3(imp::kPeakThreads), 0, s, d_x, d_off, d_len,
@@ -2638,105 +2587,86 @@ extern "C" int imp_decay_knees_device(imp_ctx* ctx, const float* d_x, const int6
   return IMP_OK;
 }
 
-extern "C" int imp_decay_times(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t B,
-                               const int64_t* peak, const int64_t* knee, const double* noise_floor,
-                               const int64_t* window, double fs, double* out) {
-  if (!ctx || (B && (!x || !off || !len || !peak || !knee || !noise_floor || !window || !out)))
-    return fail(IMP_ERR_INVALID, "imp_decay_times: null argument");
+// T = double: host rows, uploaded for the call; T = float: fp32 rows that are on the device
+template <class T>
+static int decay_times_impl(imp_ctx* ctx, const char* who, const T* x, const int64_t* off, const int64_t* len, int64_t B,
+                            const int64_t* peak, const int64_t* knee, const double* noise_floor, const int64_t* window, double fs,
+                            double* out) {
+  constexpr bool resident = std::is_same<T, float>::value;
+  if (!ctx) return fail(IMP_ERR_INVALID, "%s: null ctx", who);
   IMP_CTX_LOCK(ctx);
-  if (B < 0 || !(fs > 0)) return fail(IMP_ERR_INVALID, "imp_decay_times: bad B or fs");
+  if (B && (!x || !peak || !knee || !noise_floor || !window || !out)) return fail(IMP_ERR_INVALID, "%s: null argument", who);
+  RowSpan sp;
+  int rc = rows_check(who, off, len, B, kAnyLen, &sp);
+  if (rc) return rc;
+  if (!(fs > 0)) return fail(IMP_ERR_INVALID, "%s: bad B or fs", who);
   if (B == 0) return IMP_OK;
   std::vector<imp::DecayJob> jobs((size_t)B);
-  int64_t total = 0, scr = 0;
+  int64_t scr = 0;
   for (int64_t b = 0; b < B; ++b) {
-    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in response %lld", (long long)b);
-    if (window[b] < 1) return fail(IMP_ERR_INVALID, "response %lld: window_size must be >= 1", (long long)b);
+    if (window[b] < 1) return fail(IMP_ERR_INVALID, "%s: response %lld: window_size must be >= 1", who, (long long)b);
     jobs[(size_t)b] = imp::DecayJob{off[b], len[b], peak[b], knee[b] - peak[b], window[b], noise_floor[b], scr};
     scr += 2 * (len[b] + 2);
-    total = std::max(total, off[b] + len[b]);
   }
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
+  if ((rc = ctx_bind(ctx))) return rc;
   hipStream_t s = ctx->stream;
-  const size_t bytes = (size_t)(total + scr + 4 * B) * sizeof(double) + (size_t)B * sizeof(imp::DecayJob);
+  BlockHold rows(ctx);
+  const T* d_x = x;
+  if (!resident) {
+    if ((rc = upload_rows(ctx, who, x, sp.extent, rows))) return rc;
+    d_x = (const T*)rows.p;
+  }
+  // scratch: the jobs' work arrays [scr] | out [B][4]; the jobs themselves through the staging ring
   void* buf = nullptr;
-  if ((rc = ctx_scratch(ctx, bytes, &buf))) return rc;
-  double* d_x = (double*)buf;
-  double* d_scr = d_x + total;
+  if ((rc = ctx_scratch(ctx, (size_t)(scr + 4 * B) * sizeof(double), &buf))) return rc;
+  double* d_scr = (double*)buf;
   double* d_out = d_scr + scr;
-  imp::DecayJob* d_jobs = (imp::DecayJob*)(d_out + 4 * B);
-  if (total) HIP_TRY(hipMemcpyAsync(d_x, x, (size_t)total * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), (size_t)B * sizeof(imp::DecayJob), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(imp::decay_times_kernel<double>, dim3((unsigned)B), dim3(imp::kDecayThreads), 0, s, (const double*)d_x, (const imp::DecayJob*)d_jobs, d_scr, fs, d_out);
+  void* d_jobs[1];
+  if ((rc = ctx_stage_tables(ctx, {{jobs.data(), (size_t)B * sizeof(imp::DecayJob)}}, d_jobs))) return rc;
+  hipLaunchKernelGGL(imp::decay_times_kernel<T>, dim3((unsigned)B), dim3(imp::kDecayThreads), 0, s, d_x, (const imp::DecayJob*)d_jobs[0], d_scr, fs, d_out);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)(4 * B) * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return IMP_OK;
+}
+
+extern "C" int imp_decay_times(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t B,
+                               const int64_t* peak, const int64_t* knee, const double* noise_floor,
+                               const int64_t* window, double fs, double* out) {
+  return decay_times_impl<double>(ctx, "imp_decay_times", x, off, len, B, peak, knee, noise_floor, window, fs, out);
 }
 
 extern "C" int imp_decay_times_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t B,
                                       const int64_t* peak, const int64_t* knee, const double* noise_floor,
                                       const int64_t* window, double fs, double* out) {
-  if (!ctx || (B && (!d_x || !off || !len || !peak || !knee || !noise_floor || !window || !out)))
-    return fail(IMP_ERR_INVALID, "imp_decay_times_device: null argument");
-  IMP_CTX_LOCK(ctx);
-  if (B < 0 || !(fs > 0)) return fail(IMP_ERR_INVALID, "imp_decay_times_device: bad B or fs");
-  if (B == 0) return IMP_OK;
-  std::vector<imp::DecayJob> jobs((size_t)B);
-  int64_t scr = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in response %lld", (long long)b);
-    if (window[b] < 1) return fail(IMP_ERR_INVALID, "response %lld: window_size must be >= 1", (long long)b);
-    jobs[(size_t)b] = imp::DecayJob{off[b], len[b], peak[b], knee[b] - peak[b], window[b], noise_floor[b], scr};
-    scr += 2 * (len[b] + 2);
-  }
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  const size_t bytes = (size_t)(scr + 4 * B) * sizeof(double) + (size_t)B * sizeof(imp::DecayJob);
-  void* buf = nullptr;
-  if ((rc = ctx_scratch(ctx, bytes, &buf))) return rc;
-  double* d_scr = (double*)buf;
-  double* d_out = d_scr + scr;
-  imp::DecayJob* d_jobs = (imp::DecayJob*)(d_out + 4 * B);
-  HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), (size_t)B * sizeof(imp::DecayJob), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(imp::decay_times_kernel<float>, dim3((unsigned)B), dim3(imp::kDecayThreads), 0, s, d_x, (const imp::DecayJob*)d_jobs, d_scr, fs, d_out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)(4 * B) * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return IMP_OK;
+  return decay_times_impl<float>(ctx, "imp_decay_times_device", d_x, off, len, B, peak, knee, noise_floor, window, fs, out);
 }
 
 extern "C" int imp_sosfilt(imp_ctx* ctx, const double* sos, int64_t n_sections, const double* x, const int64_t* off,
                            const int64_t* len, int64_t B, double* y) {
-  if (!ctx || !sos || (B && (!x || !off || !len || !y))) return fail(IMP_ERR_INVALID, "imp_sosfilt: null argument");
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_sosfilt: null ctx");
   IMP_CTX_LOCK(ctx);
+  if (!sos || (B && (!x || !y))) return fail(IMP_ERR_INVALID, "imp_sosfilt: null argument");
   if (n_sections < 1 || n_sections > 4096) return fail(IMP_ERR_INVALID, "imp_sosfilt: n_sections must be in [1, 4096]");
   for (int64_t s = 0; s < n_sections; ++s)
     if (sos[6 * s + 3] != 1.0) return fail(IMP_ERR_INVALID, "imp_sosfilt: section %lld is not normalised (a0 != 1)", (long long)s);
-  if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
-  if (B == 0) return IMP_OK;
-  int64_t total = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in row %lld", (long long)b);
-    total = std::max(total, off[b] + len[b]);
-  }
-  if (total == 0) return IMP_OK;
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
+  RowSpan sp;
+  int rc = rows_check("imp_sosfilt", off, len, B, kAnyLen, &sp);
+  if (rc || sp.extent == 0) return rc;
+  if ((rc = ctx_bind(ctx))) return rc;
   hipStream_t st = ctx->stream;
-  const size_t bytes = (size_t)(2 * total + 6 * n_sections) * sizeof(double) + (size_t)(2 * B) * sizeof(int64_t);
+  // scratch: x | y, one extent each; the sections and off | len through the staging ring
+  const int64_t total = sp.extent;
   void* buf = nullptr;
-  if ((rc = ctx_scratch(ctx, bytes, &buf))) return rc;
+  if ((rc = ctx_scratch(ctx, (size_t)(2 * total) * sizeof(double), &buf))) return rc;
   double* d_x = (double*)buf;
   double* d_y = d_x + total;
-  double* d_sos = d_y + total;
-  int64_t* d_off = (int64_t*)(d_sos + 6 * n_sections);
-  int64_t* d_len = d_off + B;
+  const size_t meta = (size_t)B * sizeof(int64_t);
+  void* tab[3];
+  if ((rc = ctx_stage_tables(ctx, {{sos, (size_t)(6 * n_sections) * sizeof(double)}, {off, meta}, {len, meta}}, tab))) return rc;
+  const double* d_sos = (const double*)tab[0];
+  const int64_t *d_off = (const int64_t*)tab[1], *d_len = (const int64_t*)tab[2];
   HIP_TRY(hipMemcpyAsync(d_x, x, (size_t)total * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_sos, sos, (size_t)(6 * n_sections) * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_off, off, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_len, len, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, st));
   // a cascade is its sections applied one after the other: chunks of kMaxSections ping-pong between the buffers
   for (int64_t s0 = 0; s0 < n_sections; s0 += imp::kMaxSections) {
     const int ns = (int)std::min<int64_t>(imp::kMaxSections, n_sections - s0);
@@ -2796,48 +2726,42 @@ static void iir_transition(const imp::IirSos& f, int steps, double* P) {
 
 extern "C" int imp_sosfilt_chunked(imp_ctx* ctx, const double* sos, int64_t n_sections, const double* x, const int64_t* off,
                                    const int64_t* len, int64_t B, double* y) {
-  if (!ctx || !sos || (B && (!x || !off || !len || !y))) return fail(IMP_ERR_INVALID, "imp_sosfilt_chunked: null argument");
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_sosfilt_chunked: null ctx");
   IMP_CTX_LOCK(ctx);
+  if (!sos || (B && (!x || !y))) return fail(IMP_ERR_INVALID, "imp_sosfilt_chunked: null argument");
   imp::IirSos f;
   int rc = iir_sos_from(sos, n_sections, &f, "imp_sosfilt_chunked");
   if (rc) return rc;
   if (B < 0 || B > 65535) return fail(IMP_ERR_INVALID, "imp_sosfilt_chunked: B must be in [0, 65535]");
-  if (B == 0) return IMP_OK;
-  int64_t total = 0, longest = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    if (off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in row %lld", (long long)b);
-    total = std::max(total, off[b] + len[b]);
-    longest = std::max(longest, len[b]);
-  }
-  if (total == 0 || longest == 0) return IMP_OK;
+  RowSpan sp;
+  if ((rc = rows_check("imp_sosfilt_chunked", off, len, B, kAnyLen, &sp))) return rc;
+  const int64_t total = sp.extent;
+  if (sp.maxlen == 0) return IMP_OK;
   if ((rc = ctx_bind(ctx))) return rc;
   hipStream_t st = ctx->stream;
-  const int64_t cp = (longest + imp::kIirChunk - 1) / imp::kIirChunk;
+  const int64_t cp = (sp.maxlen + imp::kIirChunk - 1) / imp::kIirChunk;
   const size_t states = (size_t)(B * cp) * imp::kIirState;
-  const size_t bytes = ((size_t)(2 * total + 256) + 2 * states) * sizeof(double) + (size_t)(2 * B) * sizeof(int64_t);
+  // scratch: x | y | chunk end states | chunk start states; the transition matrix and off | len through the staging ring
   void* buf = nullptr;
-  if ((rc = ctx_scratch(ctx, bytes, &buf))) return rc;
+  if ((rc = ctx_scratch(ctx, ((size_t)(2 * total) + 2 * states) * sizeof(double), &buf))) return rc;
   double* d_x = (double*)buf;
   double* d_y = d_x + total;
-  double* d_P = d_y + total;
-  double* d_end = d_P + 256;
+  double* d_end = d_y + total;
   double* d_init = d_end + states;
-  int64_t* d_off = (int64_t*)(d_init + states);
-  int64_t* d_len = d_off + B;
   std::vector<double> P(256);
   iir_transition(f, imp::kIirChunk, P.data());
+  const size_t meta = (size_t)B * sizeof(int64_t);
+  void* tab[3];
+  if ((rc = ctx_stage_tables(ctx, {{P.data(), 256 * sizeof(double)}, {off, meta}, {len, meta}}, tab))) return rc;
+  const double* d_P = (const double*)tab[0];
+  const int64_t *d_off = (const int64_t*)tab[1], *d_len = (const int64_t*)tab[2];
   HIP_TRY(hipMemcpyAsync(d_x, x, (size_t)total * sizeof(double), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(d_y, 0, (size_t)total * sizeof(double), st));
-  HIP_TRY(hipMemcpyAsync(d_P, P.data(), 256 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_off, off, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_len, len, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, st));
   const dim3 grid((unsigned)((cp + 63) / 64), (unsigned)B);
-  hipLaunchKernelGGL(imp::iir_chunk_end_kernel<double>, grid, dim3(64), 0, st, f, (const double*)d_x, (const int64_t*)d_off,
-                     (const int64_t*)d_len, d_end, (long long)cp);
-  hipLaunchKernelGGL(imp::iir_carry_kernel, dim3((unsigned)B), dim3(64), 0, st, (const double*)d_P, (const int64_t*)d_len,
-                     (const double*)d_end, d_init, (long long)cp);
-  hipLaunchKernelGGL(imp::iir_chunk_out_kernel<double>, grid, dim3(64), 0, st, f, (const double*)d_x, (const int64_t*)d_off,
-                     (const int64_t*)d_len, (const double*)d_init, (long long)cp, d_y);
+  hipLaunchKernelGGL(imp::iir_chunk_end_kernel<double>, grid, dim3(64), 0, st, f, (const double*)d_x, d_off, d_len, d_end, (long long)cp);
+  hipLaunchKernelGGL(imp::iir_carry_kernel, dim3((unsigned)B), dim3(64), 0, st, d_P, d_len, (const double*)d_end, d_init, (long long)cp);
+  hipLaunchKernelGGL(imp::iir_chunk_out_kernel<double>, grid, dim3(64), 0, st, f, (const double*)d_x, d_off, d_len, (const double*)d_init,
+                     (long long)cp, d_y);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(y, d_y, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -2856,9 +2780,10 @@ static int64_t xcorr_slices(int64_t nk_max) {
   const int64_t per = (int64_t)imp::kXcorrThreads * imp::kXcorrLags;
   return std::max<int64_t>(1, (nk_max + per - 1) / per);
 }
-// the pairs' checks and launch size: *nk = longest a_len + b_len, *lds_doubles = what launch_xcorr requests
-static int xcorr_check_pairs(const int64_t* a_off, const int64_t* a_len, const int64_t* b_off, const int64_t* b_len, int64_t B,
-                             int64_t* nk, int64_t* lds_doubles) {
+// the pairs' checks and launch size: *nk = longest a_len + b_len, *lds_doubles = what launch_xcorr requests, *sa / *sb =
+// what the two sides' segments span
+static int xcorr_check_pairs(const char* who, const int64_t* a_off, const int64_t* a_len, const int64_t* b_off, const int64_t* b_len,
+                             int64_t B, int64_t* nk, int64_t* lds_doubles, RowSpan* sa, RowSpan* sb) {
   *nk = 0;
   *lds_doubles = 0;
   for (int64_t p = 0; p < B; ++p) {
@@ -2870,7 +2795,8 @@ static int xcorr_check_pairs(const int64_t* a_off, const int64_t* a_len, const i
     *nk = std::max(*nk, a_len[p] + b_len[p]);
     *lds_doubles = std::max(*lds_doubles, (int64_t)imp::xcorr_lds_doubles(a_len[p], b_len[p]));
   }
-  return IMP_OK;
+  int rc = rows_check(who, a_off, a_len, B, kAnyLen, sa);
+  return rc ? rc : rows_check(who, b_off, b_len, B, kAnyLen, sb);
 }
 template <class Sample>
 static int launch_xcorr(imp_ctx* ctx, hipStream_t s, const Sample* a, const int64_t* a_off, const int64_t* a_len, const Sample* b,
@@ -2888,44 +2814,40 @@ static int launch_xcorr(imp_ctx* ctx, hipStream_t s, const Sample* a, const int6
   return IMP_OK;
 }
 
-extern "C" int imp_xcorr_argmax(imp_ctx* ctx, const double* a, const int64_t* a_off, const int64_t* a_len,
-                                const double* b, const int64_t* b_off, const int64_t* b_len, int64_t B,
-                                int64_t* arg_out, double* val_out) {
-  if (!ctx || (B && (!a || !a_off || !a_len || !b || !b_off || !b_len || !arg_out)))
-    return fail(IMP_ERR_INVALID, "imp_xcorr_argmax: null argument");
-  if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
-  if (B == 0) return IMP_OK;
-  int64_t ta = 0, tb = 0, lds = 0, lds_doubles = 0;
-  int rc = xcorr_check_pairs(a_off, a_len, b_off, b_len, B, &lds, &lds_doubles);
-  if (rc) return rc;
-  for (int64_t p = 0; p < B; ++p) {
-    ta = std::max(ta, a_off[p] + a_len[p]);
-    tb = std::max(tb, b_off[p] + b_len[p]);
-  }
-  rc = ctx_bind(ctx);
-  if (rc) return rc;
+// T = double: host segments a, b, uploaded for the call; T = float: segments of fp32 rows that are on the device
+template <class T>
+static int xcorr_argmax_impl(imp_ctx* ctx, const char* who, const T* a, const int64_t* a_off, const int64_t* a_len, const T* b,
+                             const int64_t* b_off, const int64_t* b_len, int64_t B, int64_t* arg_out, double* val_out) {
+  constexpr bool resident = std::is_same<T, float>::value;
+  if (!ctx) return fail(IMP_ERR_INVALID, "%s: null ctx", who);
   IMP_CTX_LOCK(ctx);
+  if (B && (!a || !a_off || !a_len || !b || !b_off || !b_len || !arg_out)) return fail(IMP_ERR_INVALID, "%s: null argument", who);
+  if (B < 0) return fail(IMP_ERR_INVALID, "%s: B < 0", who);
+  if (B == 0) return IMP_OK;
+  int64_t nk = 0, lds_doubles = 0;
+  RowSpan sa, sb;
+  int rc = xcorr_check_pairs(who, a_off, a_len, b_off, b_len, B, &nk, &lds_doubles, &sa, &sb);
+  if (rc || (rc = ctx_bind(ctx))) return rc;
   hipStream_t s = ctx->stream;
-  // scratch: a, b (fp64), 4 x int64 meta, arg (int64), val (fp64)
-  const size_t meta = (size_t)B * sizeof(int64_t);
-  const int64_t S = xcorr_slices(lds - 1);
-  const size_t bytes = (size_t)(ta + tb) * sizeof(double) + 6 * meta + 2 * (size_t)(B * S) * 8;
+  BlockHold rows_a(ctx), rows_b(ctx);
+  if (!resident) {
+    if ((rc = upload_rows(ctx, who, a, sa.extent, rows_a)) || (rc = upload_rows(ctx, who, b, sb.extent, rows_b))) return rc;
+    a = (const T*)rows_a.p;
+    b = (const T*)rows_b.p;
+  }
+  // scratch: arg [B] | val [B] | the slices' partial argmax [B][S] | their values [B][S]; the four tables through the staging ring
+  const int64_t S = xcorr_slices(nk - 1);
   void* scr = nullptr;
-  if ((rc = ctx_scratch(ctx, bytes, &scr))) return rc;
-  double* d_a = (double*)scr;
-  double* d_b = d_a + ta;
-  int64_t* d_meta = (int64_t*)(d_b + tb);
-  long long* d_arg = (long long*)(d_meta + 4 * B);
+  if ((rc = ctx_scratch(ctx, 2 * (size_t)(B + B * S) * 8, &scr))) return rc;
+  long long* d_arg = (long long*)scr;
   double* d_val = (double*)(d_arg + B);
   long long* d_pk = (long long*)(d_val + B);
   double* d_pv = (double*)(d_pk + B * S);
-  HIP_TRY(hipMemcpyAsync(d_a, a, (size_t)ta * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_b, b, (size_t)tb * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_meta, a_off, meta, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_meta + B, a_len, meta, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_meta + 2 * B, b_off, meta, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_meta + 3 * B, b_len, meta, hipMemcpyHostToDevice, s));
-  if ((rc = launch_xcorr<double>(ctx, s, d_a, d_meta, d_meta + B, d_b, d_meta + 2 * B, d_meta + 3 * B, B, lds_doubles, lds - 1, d_pk, d_pv, d_arg, d_val)))
+  const size_t meta = (size_t)B * sizeof(int64_t);
+  void* tab[4];
+  if ((rc = ctx_stage_tables(ctx, {{a_off, meta}, {a_len, meta}, {b_off, meta}, {b_len, meta}}, tab))) return rc;
+  if ((rc = launch_xcorr<T>(ctx, s, a, (const int64_t*)tab[0], (const int64_t*)tab[1], b, (const int64_t*)tab[2], (const int64_t*)tab[3], B,
+                            lds_doubles, nk - 1, d_pk, d_pv, d_arg, d_val)))
     return rc;
   std::vector<long long> h_arg((size_t)B);
   std::vector<double> h_val((size_t)B);
@@ -2939,50 +2861,22 @@ extern "C" int imp_xcorr_argmax(imp_ctx* ctx, const double* a, const int64_t* a_
   return IMP_OK;
 }
 
+extern "C" int imp_xcorr_argmax(imp_ctx* ctx, const double* a, const int64_t* a_off, const int64_t* a_len,
+                                const double* b, const int64_t* b_off, const int64_t* b_len, int64_t B,
+                                int64_t* arg_out, double* val_out) {
+  return xcorr_argmax_impl<double>(ctx, "imp_xcorr_argmax", a, a_off, a_len, b, b_off, b_len, B, arg_out, val_out);
+}
+
 extern "C" int imp_xcorr_argmax_device(imp_ctx* ctx, const float* d_x, const int64_t* a_off, const int64_t* a_len,
                                        const int64_t* b_off, const int64_t* b_len, int64_t B, int64_t* arg_out, double* val_out) {
-  if (!ctx || (B && (!d_x || !a_off || !a_len || !b_off || !b_len || !arg_out)))
-    return fail(IMP_ERR_INVALID, "imp_xcorr_argmax_device: null argument");
-  if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
-  if (B == 0) return IMP_OK;
-  int64_t lds = 0, lds_doubles = 0;
-  int rc = xcorr_check_pairs(a_off, a_len, b_off, b_len, B, &lds, &lds_doubles);
-  if (rc) return rc;
-  IMP_CTX_LOCK(ctx);
-  rc = ctx_bind(ctx);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  const size_t meta = (size_t)B * sizeof(int64_t);
-  const int64_t S = xcorr_slices(lds - 1);
-  void* scr = nullptr;
-  if ((rc = ctx_scratch(ctx, 6 * meta + 2 * (size_t)(B * S) * 8, &scr))) return rc;
-  int64_t* d_meta = (int64_t*)scr;
-  long long* d_arg = (long long*)(d_meta + 4 * B);
-  double* d_val = (double*)(d_arg + B);
-  long long* d_pk = (long long*)(d_val + B);
-  double* d_pv = (double*)(d_pk + B * S);
-  HIP_TRY(hipMemcpyAsync(d_meta, a_off, meta, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_meta + B, a_len, meta, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_meta + 2 * B, b_off, meta, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_meta + 3 * B, b_len, meta, hipMemcpyHostToDevice, s));
-  if ((rc = launch_xcorr<float>(ctx, s, d_x, d_meta, d_meta + B, d_x, d_meta + 2 * B, d_meta + 3 * B, B, lds_doubles, lds - 1, d_pk, d_pv, d_arg, d_val)))
-    return rc;
-  std::vector<long long> h_arg((size_t)B);
-  std::vector<double> h_val((size_t)B);
-  HIP_TRY(hipMemcpyAsync(h_arg.data(), d_arg, (size_t)B * sizeof(long long), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(h_val.data(), d_val, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  for (int64_t p = 0; p < B; ++p) {
-    arg_out[p] = (int64_t)h_arg[(size_t)p];
-    if (val_out) val_out[p] = h_val[(size_t)p];
-  }
-  return IMP_OK;
+  return xcorr_argmax_impl<float>(ctx, "imp_xcorr_argmax_device", d_x, a_off, a_len, d_x, b_off, b_len, B, arg_out, val_out);
 }
 
 extern "C" int imp_debug_xcorr_lds(int64_t na, int64_t nb, int64_t* requested, int64_t* needed) {
   const int64_t off = 0;
   int64_t nk = 0, lds_doubles = 0;
-  int rc = xcorr_check_pairs(&off, &na, &off, &nb, 1, &nk, &lds_doubles);
+  RowSpan sa, sb;
+  int rc = xcorr_check_pairs("imp_debug_xcorr_lds", &off, &na, &off, &nb, 1, &nk, &lds_doubles, &sa, &sb);
   if (rc) return rc;
   if (lds_doubles > xcorr_lds_cap())
     return fail(IMP_ERR_UNSUPPORTED, "(%lld, %lld): the launch requests %lld doubles, over the %lld the lag search is opted in to",
@@ -2996,125 +2890,83 @@ extern "C" int imp_debug_xcorr_lds(int64_t na, int64_t nb, int64_t* requested, i
 
 extern "C" int imp_shift_rows_device(imp_ctx* ctx, const float* d_src, const int64_t* src_off, const int64_t* len,
                                      const int64_t* shift, int64_t B, float* d_dst, const int64_t* dst_off) {
-  if (!ctx || (B && (!d_src || !src_off || !len || !shift || !d_dst || !dst_off)))
-    return fail(IMP_ERR_INVALID, "imp_shift_rows_device: null argument");
-  if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
-  if (B == 0) return IMP_OK;
-  int64_t longest = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    if (src_off[b] < 0 || dst_off[b] < 0 || len[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in row %lld", (long long)b);
-    longest = std::max(longest, len[b]);
-  }
-  if (longest == 0) return IMP_OK;
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_shift_rows_device: null ctx");
   IMP_CTX_LOCK(ctx);
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
-  void *h = nullptr, *d = nullptr;
+  if (B && (!d_src || !shift || !d_dst)) return fail(IMP_ERR_INVALID, "imp_shift_rows_device: null argument");
+  RowSpan sp, dst;
+  int rc = rows_check("imp_shift_rows_device", src_off, len, B, kAnyLen, &sp);
+  if (rc || (rc = rows_check("imp_shift_rows_device", dst_off, len, B, kAnyLen, &dst))) return rc;
+  if (sp.maxlen == 0) return IMP_OK;
+  if ((rc = ctx_bind(ctx))) return rc;
   const size_t meta = (size_t)B * sizeof(int64_t);
-  if ((rc = ctx_stage(ctx, 4 * meta, &h, &d))) return rc;
-  int64_t* hm = (int64_t*)h;
-  std::memcpy(hm, src_off, meta);
-  std::memcpy(hm + B, len, meta);
-  std::memcpy(hm + 2 * B, shift, meta);
-  std::memcpy(hm + 3 * B, dst_off, meta);
-  if ((rc = ctx_stage_push(ctx, h, d, 4 * meta))) return rc;
-  const int64_t* dm = (const int64_t*)d;
-  hipLaunchKernelGGL(imp::shift_rows_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (longest + 1023) / 1024)), (unsigned)B), dim3(256), 0,
-                     ctx->stream, d_src, dm, dm + B, (const long long*)nullptr, (const long long*)(dm + 2 * B), d_dst, dm + 3 * B);
+  void* tab[4];
+  if ((rc = ctx_stage_tables(ctx, {{src_off, meta}, {len, meta}, {shift, meta}, {dst_off, meta}}, tab))) return rc;
+  hipLaunchKernelGGL(imp::shift_rows_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (sp.maxlen + 1023) / 1024)), (unsigned)B), dim3(256), 0,
+                     ctx->stream, d_src, (const int64_t*)tab[0], (const int64_t*)tab[1], (const long long*)nullptr, (const long long*)tab[2], d_dst,
+                     (const int64_t*)tab[3]);
   HIP_TRY(hipGetLastError());
+  return IMP_OK;
+}
+
+// the fades and the decay window of every row against its length
+static int window_check(const imp_window_params* params, const int64_t* len, int64_t B) {
+  for (int64_t b = 0; b < B; ++b) {
+    if (params[b].fade_in < 0 || params[b].fade_out < 0 || params[b].fade_in > len[b] || params[b].fade_out > len[b])
+      return fail(IMP_ERR_INVALID, "fade longer than row %lld", (long long)b);
+    // numpy would raise on the concatenate/multiply length mismatch (core/decay.py:391-402)
+    if (params[b].decay_half >= 0 && (params[b].decay_start < 0 || params[b].decay_knee > len[b] ||
+                                      params[b].decay_start + params[b].decay_half != params[b].decay_knee))
+      return fail(IMP_ERR_INVALID, "decay window of row %lld does not tile the row", (long long)b);
+  }
   return IMP_OK;
 }
 
 extern "C" int imp_apply_window(imp_ctx* ctx, float* x, const int64_t* off, const int64_t* len, int64_t B,
                                 const imp_window_params* params) {
-  if (!ctx || (B && (!x || !off || !len || !params))) return fail(IMP_ERR_INVALID, "imp_apply_window: null argument");
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_apply_window: null ctx");
   IMP_CTX_LOCK(ctx);
-  if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
-  if (B == 0) return IMP_OK;
-  int64_t total = 0, maxlen = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    if (len[b] < 0 || off[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in row %lld", (long long)b);
-    if (params[b].fade_in < 0 || params[b].fade_out < 0 || params[b].fade_in > len[b] || params[b].fade_out > len[b])
-      return fail(IMP_ERR_INVALID, "fade longer than row %lld", (long long)b);
-    if (params[b].decay_half >= 0) {
-      // numpy would raise on the concatenate/multiply length mismatch (core/decay.py:391-402)
-      if (params[b].decay_start < 0 || params[b].decay_knee > len[b] ||
-          params[b].decay_start + params[b].decay_half != params[b].decay_knee)
-        return fail(IMP_ERR_INVALID, "decay window of row %lld does not tile the row", (long long)b);
-    }
-    total = std::max(total, off[b] + len[b]);
-    maxlen = std::max(maxlen, len[b]);
-  }
-  if (total == 0) return IMP_OK;
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
+  if (B && (!x || !params)) return fail(IMP_ERR_INVALID, "imp_apply_window: null argument");
+  RowSpan sp;
+  int rc = rows_check("imp_apply_window", off, len, B, kAnyLen, &sp);
+  if (rc || (rc = window_check(params, len, B))) return rc;
+  if (sp.extent == 0) return IMP_OK;
+  if ((rc = ctx_bind(ctx))) return rc;
   hipStream_t s = ctx->stream;
-  float* d_x = nullptr;
-  if ((rc = ctx_block_get(ctx, (size_t)total * sizeof(float), (void**)&d_x))) return rc;
-  auto cleanup = [&](int code) {
-    (void)hipStreamSynchronize(s);
-    (void)ctx_block_put(ctx, d_x);
-    return code;
-  };
+  BlockHold rows(ctx);
+  if ((rc = upload_rows(ctx, "imp_apply_window", x, sp.extent, rows))) return rc;
+  float* d_x = (float*)rows.p;
   const size_t meta = (size_t)B * sizeof(int64_t);
-  void* scr = nullptr;
-  if ((rc = ctx_scratch(ctx, 2 * meta + (size_t)B * sizeof(imp_window_params), &scr))) return cleanup(rc);
-  int64_t* d_off = (int64_t*)scr;
-  int64_t* d_len = d_off + B;
-  imp_window_params* d_par = (imp_window_params*)(d_len + B);
-  if (hipMemcpyAsync(d_x, x, (size_t)total * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(d_off, off, meta, hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(d_len, len, meta, hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(d_par, params, (size_t)B * sizeof(imp_window_params), hipMemcpyHostToDevice, s) != hipSuccess)
-    return cleanup(fail(IMP_ERR_HIP, "imp_apply_window: h2d copy failed"));
-  const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(256, (maxlen + 1023) / 1024));
+  void* tab[3];
+  if ((rc = ctx_stage_tables(ctx, {{off, meta}, {len, meta}, {params, (size_t)B * sizeof(imp_window_params)}}, tab))) return rc;
+  const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(256, (sp.maxlen + 1023) / 1024));
   dim3 grid((unsigned)bpr, (unsigned)B), block(256);
-  hipLaunchKernelGGL(imp::apply_window_kernel, grid, block, 0, s, d_x, d_off, d_len,
-                     reinterpret_cast<const imp::WindowParams*>(d_par));
-  if (hipGetLastError() != hipSuccess) return cleanup(fail(IMP_ERR_HIP, "apply_window launch failed"));
-  if (hipMemcpyAsync(x, d_x, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess)
-    return cleanup(fail(IMP_ERR_HIP, "imp_apply_window: d2h copy failed"));
-  return cleanup(IMP_OK);
+  hipLaunchKernelGGL(imp::apply_window_kernel, grid, block, 0, s, d_x, (const int64_t*)tab[0], (const int64_t*)tab[1],
+                     (const imp::WindowParams*)tab[2]);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(x, d_x, (size_t)sp.extent * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return IMP_OK;
 }
 
 extern "C" int imp_apply_window_device(imp_ctx* ctx, const float* d_src, const int64_t* src_off, float* d_dst,
                                        const int64_t* dst_off, const int64_t* len, int64_t B,
                                        const imp_window_params* params) {
-  if (!ctx || (B && (!d_src || !d_dst || !src_off || !dst_off || !len || !params)))
-    return fail(IMP_ERR_INVALID, "imp_apply_window_device: null argument");
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_apply_window_device: null ctx");
   IMP_CTX_LOCK(ctx);
-  if (B < 0) return fail(IMP_ERR_INVALID, "B < 0");
-  if (B == 0) return IMP_OK;
-  int64_t maxlen = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    if (len[b] < 0 || src_off[b] < 0 || dst_off[b] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in row %lld", (long long)b);
-    if (params[b].fade_in < 0 || params[b].fade_out < 0 || params[b].fade_in > len[b] || params[b].fade_out > len[b])
-      return fail(IMP_ERR_INVALID, "fade longer than row %lld", (long long)b);
-    if (params[b].decay_half >= 0 && (params[b].decay_start < 0 || params[b].decay_knee > len[b] ||
-                                      params[b].decay_start + params[b].decay_half != params[b].decay_knee))
-      return fail(IMP_ERR_INVALID, "decay window of row %lld does not tile the row", (long long)b);
-    maxlen = std::max(maxlen, len[b]);
-  }
-  if (maxlen == 0) return IMP_OK;
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  const size_t meta = (size_t)B * sizeof(int64_t);
+  if (B && (!d_src || !d_dst || !params)) return fail(IMP_ERR_INVALID, "imp_apply_window_device: null argument");
+  RowSpan sp, dst;
+  int rc = rows_check("imp_apply_window_device", src_off, len, B, kAnyLen, &sp);
+  if (rc || (rc = rows_check("imp_apply_window_device", dst_off, len, B, kAnyLen, &dst)) || (rc = window_check(params, len, B))) return rc;
+  if (sp.maxlen == 0) return IMP_OK;
+  if ((rc = ctx_bind(ctx))) return rc;
   // the tables travel through the staging ring: one copy, and the call returns without waiting for the device
-  const size_t tab_bytes = 3 * meta + (size_t)B * sizeof(imp_window_params);
-  int64_t *h_tab = nullptr, *d_so = nullptr;
-  if ((rc = ctx_stage(ctx, tab_bytes, (void**)&h_tab, (void**)&d_so))) return rc;
-  int64_t* d_do = d_so + B;
-  int64_t* d_len = d_do + B;
-  imp_window_params* d_par = (imp_window_params*)(d_len + B);
-  std::memcpy(h_tab, src_off, meta);
-  std::memcpy(h_tab + B, dst_off, meta);
-  std::memcpy(h_tab + 2 * B, len, meta);
-  std::memcpy(h_tab + 3 * B, params, (size_t)B * sizeof(imp_window_params));
-  if ((rc = ctx_stage_push(ctx, h_tab, d_so, tab_bytes))) return rc;
-  const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(256, (maxlen + 1023) / 1024));
-  hipLaunchKernelGGL(imp::apply_window_copy_kernel, dim3((unsigned)bpr, (unsigned)B), dim3(256), 0, s, d_src, d_so, d_dst, d_do,
-                     d_len, reinterpret_cast<const imp::WindowParams*>(d_par));
+  const size_t meta = (size_t)B * sizeof(int64_t);
+  void* tab[4];
+  if ((rc = ctx_stage_tables(ctx, {{src_off, meta}, {dst_off, meta}, {len, meta}, {params, (size_t)B * sizeof(imp_window_params)}}, tab)))
+    return rc;
+  const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(256, (sp.maxlen + 1023) / 1024));
+  hipLaunchKernelGGL(imp::apply_window_copy_kernel, dim3((unsigned)bpr, (unsigned)B), dim3(256), 0, ctx->stream, d_src, (const int64_t*)tab[0],
+                     d_dst, (const int64_t*)tab[1], (const int64_t*)tab[2], (const imp::WindowParams*)tab[3]);
   HIP_TRY(hipGetLastError());
   return IMP_OK;
 }
@@ -3122,44 +2974,32 @@ extern "C" int imp_apply_window_device(imp_ctx* ctx, const float* d_src, const i
 extern "C" int imp_rows_to_pcm_device(imp_ctx* ctx, const float* d_rows, const int64_t* off, const int64_t* len,
                                       int64_t n_rows, const int64_t* row_of_track, int64_t n_tracks, int64_t n_frames,
                                       int bits, void* pcm_out) {
-  if (!ctx || !d_rows || !off || !len || !row_of_track || !pcm_out)
-    return fail(IMP_ERR_INVALID, "imp_rows_to_pcm_device: null argument");
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_rows_to_pcm_device: null ctx");
   IMP_CTX_LOCK(ctx);
+  if (!d_rows || !off || !len || !row_of_track || !pcm_out) return fail(IMP_ERR_INVALID, "imp_rows_to_pcm_device: null argument");
   if (bits != 16 && bits != 24 && bits != 32) return fail(IMP_ERR_INVALID, "Invalid bit depth. Accepted values are 16, 24 and 32.");
   if (n_rows < 0 || n_tracks < 1 || n_tracks > 4096 || n_frames < 0) return fail(IMP_ERR_INVALID, "imp_rows_to_pcm_device: bad sizes");
-  for (int64_t r = 0; r < n_rows; ++r)
-    if (off[r] < 0 || len[r] < 0) return fail(IMP_ERR_INVALID, "negative offset/length in row %lld", (long long)r);
+  RowSpan sp;
+  int rc = rows_check("imp_rows_to_pcm_device", off, len, n_rows, kAnyLen, &sp);
+  if (rc) return rc;
   for (int64_t t = 0; t < n_tracks; ++t)
     if (row_of_track[t] < -1 || row_of_track[t] >= n_rows) return fail(IMP_ERR_INVALID, "track %lld names row %lld", (long long)t, (long long)row_of_track[t]);
   if (n_frames == 0) return IMP_OK;
-  int rc = ctx_bind(ctx);
-  if (rc) return rc;
+  if ((rc = ctx_bind(ctx))) return rc;
   hipStream_t s = ctx->stream;
-  const size_t sample = bits == 16 ? 2 : 4;
-  const size_t out_bytes = (size_t)n_frames * (size_t)n_tracks * sample;
-  const size_t meta = (size_t)(2 * std::max<int64_t>(n_rows, 1) + n_tracks) * sizeof(int64_t);
-  char* d_buf = nullptr;
-  if ((rc = ctx_block_get(ctx, meta + out_bytes, (void**)&d_buf))) return rc;
-  int64_t* d_off = (int64_t*)d_buf;
-  int64_t* d_len = d_off + std::max<int64_t>(n_rows, 1);
-  int64_t* d_map = d_len + std::max<int64_t>(n_rows, 1);
-  void* d_out = d_buf + meta;
-  auto done = [&](int code) {
-    (void)hipStreamSynchronize(s);
-    (void)ctx_block_put(ctx, d_buf);
-    return code;
-  };
-  if ((n_rows && (hipMemcpyAsync(d_off, off, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-                  hipMemcpyAsync(d_len, len, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice, s) != hipSuccess)) ||
-      hipMemcpyAsync(d_map, row_of_track, (size_t)n_tracks * sizeof(int64_t), hipMemcpyHostToDevice, s) != hipSuccess)
-    return done(fail(IMP_ERR_HIP, "imp_rows_to_pcm_device: upload failed"));
+  const size_t out_bytes = (size_t)n_frames * (size_t)n_tracks * (bits == 16 ? 2 : 4);
+  BlockHold pcm(ctx);
+  if ((rc = pcm.get(out_bytes))) return rc;
+  const size_t meta = (size_t)n_rows * sizeof(int64_t);
+  void* tab[3];
+  if ((rc = ctx_stage_tables(ctx, {{off, meta}, {len, meta}, {row_of_track, (size_t)n_tracks * sizeof(int64_t)}}, tab))) return rc;
   const int64_t total = n_frames * n_tracks;
   hipLaunchKernelGGL(imp::rows_to_pcm_kernel, dim3((unsigned)std::min<int64_t>(4096, (total + 255) / 256)), dim3(256), 0, s, d_rows,
-                     d_off, d_len, d_map, (int)n_tracks, n_frames, bits, d_out);
-  if (hipGetLastError() != hipSuccess) return done(fail(IMP_ERR_HIP, "imp_rows_to_pcm_device: launch failed"));
-  if (hipMemcpyAsync(pcm_out, d_out, out_bytes, hipMemcpyDeviceToHost, s) != hipSuccess)
-    return done(fail(IMP_ERR_HIP, "imp_rows_to_pcm_device: download failed"));
-  return done(IMP_OK);
+                     (const int64_t*)tab[0], (const int64_t*)tab[1], (const int64_t*)tab[2], (int)n_tracks, n_frames, bits, pcm.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(pcm_out, pcm.p, out_bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return IMP_OK;
 }
 
 #include "slice_host.hip.inc"

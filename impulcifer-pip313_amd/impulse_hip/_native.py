@@ -265,6 +265,22 @@ def _ptr_i64(a):
     return a.ctypes.data_as(_pi64)
 
 
+def _pack(rows, dtype):
+    """Ragged rows for the native entries: (flat, offs, lens), the rows end to end in `dtype`.  A batch without samples
+    gets a one-element flat so that its .ctypes.data is a valid pointer."""
+    rows = [np.asarray(r, dtype=dtype).ravel() for r in rows]
+    lens = np.array([len(r) for r in rows], dtype=np.int64)
+    offs = np.cumsum(lens) - lens
+    flat = np.concatenate(rows) if lens.sum() else np.zeros(1, dtype=dtype)
+    return flat, offs, lens
+
+
+def _unpack(flat, lens):
+    """_pack's inverse for results: a flat array back to a list of rows (copies)."""
+    ends = np.cumsum(lens)
+    return [flat[int(e - n):int(e)].copy() for e, n in zip(ends, lens)]
+
+
 class Context:
     """One GPU + one stream (imp_ctx)."""
 
@@ -337,28 +353,14 @@ class Context:
         except Exception:
             pass
 
-    # ---- ragged helpers ------------------------------------------------------------------
-    @staticmethod
-    def _pack_rows(rows):
-        lens = np.array([len(r) for r in rows], dtype=np.int64)
-        offs = np.zeros(len(rows), dtype=np.int64)
-        if len(rows):
-            offs[1:] = np.cumsum(lens)[:-1]
-        flat = np.zeros(int(lens.sum()) if len(rows) else 0, dtype=np.float32)
-        for r, o, n in zip(rows, offs, lens):
-            flat[o:o + n] = r
-        return flat, offs, lens
-
+    # ---- ragged rows (host lists through _pack) ---------------------------------------------
     def peak_index(self, rows, peak_height=0.12589):
         """Batched ImpulseResponse.peak_index over a list of 1-D arrays. Returns (idx[int64], maxabs[f32])."""
-        rows = [np.asarray(r) for r in rows]
         B = len(rows)
         idx = np.zeros(B, dtype=np.int64)
         mx = np.zeros(B, dtype=np.float32)
-        if B == 0:
-            return idx, mx
-        flat, offs, lens = self._pack_rows(rows)
-        if flat.size == 0:
+        flat, offs, lens = _pack(rows, np.float32)
+        if lens.sum() == 0:
             return idx, mx
         _check(self._lib.imp_peak_index(self._h, _ptr_f(flat), _ptr_i64(offs), _ptr_i64(lens), B,
                                         float(peak_height), _ptr_i64(idx), _ptr_f(mx)))
@@ -378,13 +380,7 @@ class Context:
         tail = (B, int(G), int(win), int(pre), float(fs), grid.ctypes.data_as(_pd), M, raw.ctypes.data_as(_pd),
                 power.ctypes.data_as(_pd) if want_power else None)
         if dptr is None:
-            rows = [np.asarray(r, dtype=np.float64) for r in rows]
-            lens = np.array([len(r) for r in rows], dtype=np.int64)
-            offs = np.zeros(B, dtype=np.int64)
-            if B:
-                offs[1:] = np.cumsum(lens)[:-1]
-            flat = np.concatenate(rows) if int(lens.sum()) else np.zeros(1)
-            flat = np.ascontiguousarray(flat, dtype=np.float64)
+            flat, offs, lens = _pack(rows, np.float64)
             _check(self._lib.imp_mic_mismatch(self._h, flat.ctypes.data_as(_pd), _ptr_i64(offs), _ptr_i64(lens), _ptr_i64(peaks),
                                               *p32, *tail))
         else:
@@ -393,16 +389,6 @@ class Context:
             _check(self._lib.imp_mic_mismatch_device(self._h, _vp(int(dptr)), _ptr_i64(offs), _ptr_i64(lens), _ptr_i64(peaks),
                                                      *p32, *tail))
         return raw, power
-
-    @staticmethod
-    def _pack_rows64(rows):
-        rows = [np.asarray(r, dtype=np.float64).ravel() for r in rows]
-        lens = np.array([len(r) for r in rows], dtype=np.int64)
-        offs = np.zeros(len(rows), dtype=np.int64)
-        if len(rows):
-            offs[1:] = np.cumsum(lens)[:-1]
-        flat = np.ascontiguousarray(np.concatenate(rows) if int(lens.sum()) else np.zeros(1), dtype=np.float64)
-        return flat, offs, lens
 
     def binaural_metrics(self, rows, nfft, bins, D, dptr=None):
         """K15 (imp_binaural_metrics / imp_binaural_metrics_device) for P pairs, rows in the order left, right, left, ...:
@@ -421,7 +407,7 @@ class Context:
         tail = (P, _ptr_i64(nfft), _ptr_i64(bins), bands, D, band.ctypes.data_as(_pd), iacf.ctypes.data_as(_pd), _ptr_i64(peak),
                 energy.ctypes.data_as(_pd))
         if dptr is None:
-            flat, offs, lens = self._pack_rows64(rows)
+            flat, offs, lens = _pack(rows, np.float64)
             _check(self._lib.imp_binaural_metrics(self._h, flat.ctypes.data_as(_pd), _ptr_i64(offs), _ptr_i64(lens), *tail))
         else:
             offs = np.ascontiguousarray(rows[0], dtype=np.int64)
@@ -433,7 +419,7 @@ class Context:
         """K15 (imp_energy_decay_db / imp_energy_decay_db_device): the energy decay curve of every row, a list of fp64 arrays.
         rows as in binaural_metrics."""
         if dptr is None:
-            flat, offs, lens = self._pack_rows64(rows)
+            flat, offs, lens = _pack(rows, np.float64)
         else:
             offs = np.ascontiguousarray(rows[0], dtype=np.int64)
             lens = np.ascontiguousarray(rows[1], dtype=np.int64)
@@ -444,8 +430,7 @@ class Context:
         else:
             _check(self._lib.imp_energy_decay_db_device(self._h, _vp(int(dptr)), _ptr_i64(offs), _ptr_i64(lens), len(lens),
                                                         float(floor_db), out.ctypes.data_as(_pd)))
-        ends = np.cumsum(lens)
-        return [out[int(e - n):int(e)].copy() for e, n in zip(ends, lens)]
+        return _unpack(out, lens)
 
     # ---- device-resident rows (fp32 at dptr + off[b], len[b] samples) ---------------------------
     @staticmethod
@@ -534,15 +519,11 @@ class Context:
 
     def decay_times(self, rows, peaks, knees, noise_floors, windows, fs):
         """Batched core/decay.py decay_times on the device: [B, 4] = EDT, RT20, RT30, RT60 (NaN = undefined)."""
-        rows = [np.ascontiguousarray(r, dtype=np.float64).ravel() for r in rows]
         B = len(rows)
         out = np.full((B, 4), np.nan)
         if B == 0:
             return out
-        lens = np.array([len(r) for r in rows], dtype=np.int64)
-        offs = np.zeros(B, dtype=np.int64)
-        offs[1:] = np.cumsum(lens)[:-1]
-        flat = np.concatenate(rows) if lens.sum() else np.zeros(1)
+        flat, offs, lens = _pack(rows, np.float64)
         pk = np.ascontiguousarray(peaks, dtype=np.int64)
         kn = np.ascontiguousarray(knees, dtype=np.int64)
         nf = np.ascontiguousarray(noise_floors, dtype=np.float64)
@@ -592,18 +573,14 @@ class Context:
         bit-identical: within 1e-12 of the row's peak)"""
         fn = self._lib.imp_sosfilt_chunked if chunked else self._lib.imp_sosfilt
         sos = np.ascontiguousarray(sos, dtype=np.float64).reshape(-1, 6)
-        rows = [np.ascontiguousarray(r, dtype=np.float64).ravel() for r in rows]
         B = len(rows)
         if B == 0:
             return []
-        lens = np.array([len(r) for r in rows], dtype=np.int64)
-        offs = np.zeros(B, dtype=np.int64)
-        offs[1:] = np.cumsum(lens)[:-1]
-        flat = np.concatenate(rows) if lens.sum() else np.zeros(1)
+        flat, offs, lens = _pack(rows, np.float64)
         out = np.zeros_like(flat)
         _check(fn(self._h, sos.ctypes.data_as(_pd), len(sos), flat.ctypes.data_as(_pd), _ptr_i64(offs), _ptr_i64(lens), B,
                   out.ctypes.data_as(_pd)))
-        return [out[o:o + n].copy() for o, n in zip(offs, lens)]
+        return _unpack(out, lens)
 
     def xcorr_argmax(self, a_rows, b_rows):
         """np.argmax(scipy.signal.correlate(a, b, "full")) for every pair (fp64 on the device).
@@ -615,16 +592,8 @@ class Context:
         val = np.zeros(B, dtype=np.float64)
         if B == 0:
             return arg, val
-
-        def pack(rows):
-            rows = [np.ascontiguousarray(r, dtype=np.float64).ravel() for r in rows]
-            lens = np.array([len(r) for r in rows], dtype=np.int64)
-            offs = np.zeros(B, dtype=np.int64)
-            offs[1:] = np.cumsum(lens)[:-1]
-            return (np.concatenate(rows) if lens.sum() else np.zeros(1)), offs, lens
-
-        fa, oa, la = pack(a_rows)
-        fb, ob, lb = pack(b_rows)
+        fa, oa, la = _pack(a_rows, np.float64)
+        fb, ob, lb = _pack(b_rows, np.float64)
         _check(self._lib.imp_xcorr_argmax(self._h, fa.ctypes.data_as(_pd), _ptr_i64(oa), _ptr_i64(la),
                                           fb.ctypes.data_as(_pd), _ptr_i64(ob), _ptr_i64(lb), B,
                                           _ptr_i64(arg), val.ctypes.data_as(_pd)))
@@ -677,18 +646,12 @@ class Context:
 
     def apply_window(self, rows, params):
         """In-place-style windowing of a list of rows; returns new float32 arrays."""
-        rows = [np.asarray(r) for r in rows]
         B = len(rows)
         if B == 0:
             return []
-        flat, offs, lens = self._pack_rows(rows)
-        arr = (WindowParams * B)()
-        for i, p in enumerate(params):
-            arr[i] = WindowParams(float(p.get("gain", 1.0)), int(p.get("fade_in", 0)), int(p.get("fade_out", 0)),
-                                  int(p.get("decay_start", 0)), int(p.get("decay_half", -1)),
-                                  int(p.get("decay_knee", 0)), float(p.get("decay_level_db", 0.0)))
-        _check(self._lib.imp_apply_window(self._h, _ptr_f(flat), _ptr_i64(offs), _ptr_i64(lens), B, arr))
-        return [flat[o:o + n].copy() for o, n in zip(offs, lens)]
+        flat, offs, lens = _pack(rows, np.float32)
+        _check(self._lib.imp_apply_window(self._h, _ptr_f(flat), _ptr_i64(offs), _ptr_i64(lens), B, self._window_array(params, B)))
+        return _unpack(flat, lens)
 
 
 class SegSet:
@@ -698,13 +661,8 @@ class SegSet:
     def __init__(self, ctx, rows):
         self.ctx = ctx
         self._lib = ctx._lib
-        rows = [np.ascontiguousarray(r, dtype=np.float64).ravel() for r in rows]
-        self.lens = np.array([len(r) for r in rows], dtype=np.int64)
-        B = len(rows)
-        offs = np.zeros(max(B, 1), dtype=np.int64)[:B]
-        if B:
-            offs[1:] = np.cumsum(self.lens)[:-1]
-        flat = np.concatenate(rows) if B and self.lens.sum() else np.zeros(1)
+        flat, offs, self.lens = _pack(rows, np.float64)
+        B = len(self.lens)
         self.maxabs = np.zeros(max(B, 1), dtype=np.float64)[:B]
         h = _vp()
         _check(self._lib.imp_segset_create(ctx.handle, flat.ctypes.data_as(_pd), _ptr_i64(offs), _ptr_i64(self.lens), B,
