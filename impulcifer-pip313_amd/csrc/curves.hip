@@ -157,6 +157,7 @@ __global__ __launch_bounds__(kT) void curves_eq_kernel(EqArgs a) {
   }
   __syncthreads();
   if (!a.smoothen_kinks) {
+    if (a.spline_used && threadIdx.x == 0) a.spline_used[blockIdx.x] = 0;
     for (int i = threadIdx.x; i < n; i += kT) a.equalization[base + i] = e[i];
     return;
   }
@@ -175,10 +176,13 @@ __global__ __launch_bounds__(kT) void curves_eq_kernel(EqArgs a) {
   }
   __syncthreads();
   const int n_doomed = s_cnt;
-  if (a.spline_used && threadIdx.x == 0) a.spline_used[blockIdx.x] = n_doomed > 0;
-  if (n_doomed == 0) {
-    // the reference still runs the interpolating spline through ALL points and reads it back at those points:
-    // the data again, to rounding
+  // fewer than 3 survivors (the last two are always kept): a quadratic spline does not exist, the reference raises
+  // (FITPACK: m > k).  The flag says so (2) and the clipped curve goes out unbridged; who downloads the flags refuses.
+  const bool too_few = n - n_doomed < 3;
+  if (a.spline_used && threadIdx.x == 0) a.spline_used[blockIdx.x] = too_few ? 2 : n_doomed > 0;
+  if (n_doomed == 0 || too_few) {
+    // nothing dropped: the reference still runs the interpolating spline through ALL points and reads it back at
+    // those points: the data again, to rounding
     for (int i = threadIdx.x; i < n; i += kT) a.equalization[base + i] = e[i];
     return;
   }
@@ -491,9 +495,12 @@ static int curves_equalization_device(imp_curves* c, const double* error, int64_
                                                   : "NaN values detected during equalization, interpolating data with default parameters.");
   int rc;
   EqArgs a{};
-  if ((rc = curves_window(c, 1.0 / 6, &a.w6)) || (rc = curves_window(c, 1.0 / 3, &a.w3)) || (rc = curves_window(c, 1.3, &a.w130)) ||
-      (rc = curves_sigmoid(c, 100.0, 10000.0, 0.0, 1.0, &a.k_light)) || (rc = curves_sigmoid(c, 1000.0, 6000.0, 0.0, 1.0, &a.k_heavy)) ||
-      (rc = curves_sigmoid(c, treble_f_lower, treble_f_upper, max_gain, treble_max_gain, &a.limit)) ||
+  // the smoothing windows are asked for only when they are used: equalize() alone also runs on grids too coarse for them
+  if (smoothen_first &&
+      ((rc = curves_window(c, 1.0 / 6, &a.w6)) || (rc = curves_window(c, 1.0 / 3, &a.w3)) || (rc = curves_window(c, 1.3, &a.w130)) ||
+       (rc = curves_sigmoid(c, 100.0, 10000.0, 0.0, 1.0, &a.k_light)) || (rc = curves_sigmoid(c, 1000.0, 6000.0, 0.0, 1.0, &a.k_heavy))))
+    return rc;
+  if ((rc = curves_sigmoid(c, treble_f_lower, treble_f_upper, max_gain, treble_max_gain, &a.limit)) ||
       (rc = curves_sigmoid(c, treble_f_lower, treble_f_upper, 1.0, treble_gain_k, &a.gain_k)) || (rc = curves_reserve(c, B)))
     return rc;
   if ((rc = ctx_kernel_lds(c->ctx, reinterpret_cast<const void*>(curves_eq_kernel), kEqLds))) return rc;
@@ -530,8 +537,15 @@ extern "C" int imp_curves_equalization(imp_curves* c, const double* error, int64
   const size_t bytes = (size_t)B * c->n * sizeof(double);
   if (error_smoothed_out) HIP_TRY(hipMemcpyAsync(error_smoothed_out, c->d_b, bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(equalization_out, c->d_c, bytes, hipMemcpyDeviceToHost, s));
-  if (spline_used_out) HIP_TRY(hipMemcpyAsync(spline_used_out, c->d_flags, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+  std::vector<int> flags((size_t)B);
+  HIP_TRY(hipMemcpyAsync(flags.data(), c->d_flags, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  if (spline_used_out) std::copy(flags.begin(), flags.end(), spline_used_out);
+  if (smoothen_kinks)
+    for (int64_t b = 0; b < B; ++b)
+      if (flags[(size_t)b] == 2)
+        return fail(IMP_ERR_INVALID, "imp_curves_equalization: curve %lld keeps fewer than 3 points after the kink rule "
+                    "(the quadratic spline needs at least 3)", (long long)b);
   return IMP_OK;
 }
 

@@ -1019,6 +1019,13 @@ class Curves:
         self._h = h
         ctx._plans.add(self)
 
+    def _live(self):
+        """the native handle; a handle that was closed (curves_for evicts the oldest grid beyond 8) refuses by name"""
+        if not self._h:
+            raise RuntimeError("this Curves handle is closed (evicted from the curves_for cache, or its context was closed): "
+                               "ask curves_for(frequency) for a live one")
+        return self._h
+
     def _rows(self, x):
         a = np.ascontiguousarray(x, dtype=np.float64)
         one = a.ndim == 1
@@ -1030,13 +1037,13 @@ class Curves:
 
     def window_size(self, octaves):
         w = C.c_int(0)
-        _check(self._lib.imp_curves_window_size(self._h, float(octaves), C.byref(w)))
+        _check(self._lib.imp_curves_window_size(self._live(), float(octaves), C.byref(w)))
         return w.value
 
     def smooth(self, x, window_oct, treble_window_oct, treble_f_lower, treble_f_upper):
         a, one = self._rows(x)
         y = np.empty_like(a)
-        _check(self._lib.imp_curves_smooth(self._h, a.ctypes.data_as(_pd), a.shape[0], float(window_oct),
+        _check(self._lib.imp_curves_smooth(self._live(), a.ctypes.data_as(_pd), a.shape[0], float(window_oct),
                                            float(treble_window_oct), float(treble_f_lower), float(treble_f_upper),
                                            y.ctypes.data_as(_pd)))
         return y[0] if one else y
@@ -1047,7 +1054,7 @@ class Curves:
         a, one = self._rows(error)
         es, eq = np.empty_like(a), np.empty_like(a)
         used = np.zeros(a.shape[0], dtype=np.int32)
-        _check(self._lib.imp_curves_equalization(self._h, a.ctypes.data_as(_pd), a.shape[0], 1 if smoothen_first else 0,
+        _check(self._lib.imp_curves_equalization(self._live(), a.ctypes.data_as(_pd), a.shape[0], 1 if smoothen_first else 0,
                                                  float(max_gain), float(treble_f_lower), float(treble_f_upper),
                                                  float(treble_max_gain), float(treble_gain_k), 1 if smoothen_kinks else 0,
                                                  es.ctypes.data_as(_pd), eq.ctypes.data_as(_pd),
@@ -1056,7 +1063,7 @@ class Curves:
 
     def fir_taps(self, fs, f_res):
         n = _i64()
-        _check(self._lib.imp_curves_fir_taps(self._h, float(fs), float(f_res), C.byref(n)))
+        _check(self._lib.imp_curves_fir_taps(self._live(), float(fs), float(f_res), C.byref(n)))
         return n.value
 
     def fir(self, equalization, fs, f_res, normalize, want_gain=False):
@@ -1064,7 +1071,7 @@ class Curves:
         taps = self.fir_taps(fs, f_res)
         fir = np.empty((a.shape[0], taps), dtype=np.float64)
         gain = np.empty_like(fir) if want_gain else None
-        _check(self._lib.imp_curves_fir(self._h, a.ctypes.data_as(_pd), a.shape[0], float(fs), float(f_res),
+        _check(self._lib.imp_curves_fir(self._live(), a.ctypes.data_as(_pd), a.shape[0], float(fs), float(f_res),
                                         1 if normalize else 0, gain.ctypes.data_as(_pd) if want_gain else None,
                                         fir.ctypes.data_as(_pd)))
         if want_gain:
@@ -1078,7 +1085,7 @@ class Curves:
         taps = self.fir_taps(fs, f_res)
         eq = np.empty_like(a)
         fir = np.empty((a.shape[0], taps), dtype=np.float64)
-        _check(self._lib.imp_curves_equalization_fir(self._h, a.ctypes.data_as(_pd), a.shape[0], 1 if smoothen_first else 0,
+        _check(self._lib.imp_curves_equalization_fir(self._live(), a.ctypes.data_as(_pd), a.shape[0], 1 if smoothen_first else 0,
                                                      float(max_gain), float(treble_f_lower), float(treble_f_upper),
                                                      float(treble_max_gain), float(treble_gain_k),
                                                      1 if smoothen_kinks else 0, float(fs), float(f_res),
@@ -1093,7 +1100,7 @@ class Curves:
         d = _vp()
         taps = _i64()
         _check(self._lib.imp_curves_equalization_fir_device(
-            self._h, a.ctypes.data_as(_pd), a.shape[0], 1 if smoothen_first else 0, float(max_gain), float(treble_f_lower),
+            self._live(), a.ctypes.data_as(_pd), a.shape[0], 1 if smoothen_first else 0, float(max_gain), float(treble_f_lower),
             float(treble_f_upper), float(treble_max_gain), float(treble_gain_k), 1 if smoothen_kinks else 0, float(fs), float(f_res),
             1 if normalize else 0, eq.ctypes.data_as(_pd) if want_equalization else None, C.byref(d), C.byref(taps)))
         return eq, DeviceFirs(self.ctx, d.value, a.shape[0], taps.value)

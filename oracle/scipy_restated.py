@@ -161,15 +161,17 @@ def _bspline_basis_all(t, k, x):
     t = np.asarray(t, dtype=np.float64)
     x = np.asarray(x, dtype=np.float64)
     n = len(t) - k - 1
-    # degree 0: indicator of [t_i, t_{i+1}), with the last non-empty interval closed on the right
+    # degree 0: indicator of [t_i, t_{i+1}), with the last non-empty interval closed on the right; a point outside
+    # [t_0, t_end] belongs to the first / last non-empty interval, so the recursion below continues that interval's
+    # polynomial (FITPACK splev with ext = 0)
     B = np.zeros((len(x), len(t) - 1))
-    last = np.max(np.nonzero(t[1:] > t[:-1])[0])
+    nonempty = np.nonzero(t[1:] > t[:-1])[0]
+    first, last = np.min(nonempty), np.max(nonempty)
     for i in range(len(t) - 1):
         if t[i + 1] > t[i]:
-            if i == last:
-                B[:, i] = (x >= t[i]) & (x <= t[i + 1])
-            else:
-                B[:, i] = (x >= t[i]) & (x < t[i + 1])
+            lo = np.ones(len(x), dtype=bool) if i == first else x >= t[i]
+            hi = np.ones(len(x), dtype=bool) if i == last else x < t[i + 1]
+            B[:, i] = lo & hi
     for d in range(1, k + 1):
         Bn = np.zeros((len(x), len(t) - 1 - d))
         for i in range(len(t) - 1 - d):
@@ -194,7 +196,9 @@ def spline2_interp(xk, yk, xq):
     yk = np.asarray(yk, dtype=np.float64)
     xq = np.asarray(xq, dtype=np.float64)
     m = len(xk)
+    if m < 3:
+        raise ValueError("m > k must hold: a quadratic spline needs at least 3 points")
     interior = (xk[1:m - 2] + xk[2:m - 1]) / 2.0
     t = np.concatenate([[xk[0]] * 3, interior, [xk[-1]] * 3])
     coef = np.linalg.solve(_bspline_basis_all(t, 2, xk), yk)
-    return _bspline_basis_all(t, 2, np.clip(xq, xk[0], xk[-1])) @ coef
+    return _bspline_basis_all(t, 2, xq) @ coef

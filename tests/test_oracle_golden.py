@@ -598,3 +598,40 @@ def test_reflection_levels_match_the_reference_run(golden):
             for sd, v in pair.items():
                 want = g[f"{tag}_{sp}_{sd}"]
                 assert v["early_db"] == want[0] and v["late_db"] == want[1], (tag, sp, sd)
+
+
+# ------------------------------------------------------------------ K12 edges: the oracle against the reference run
+def _rel(got, want):
+    return float(np.max(np.abs(got - want)) / max(1.0, float(np.max(np.abs(want)))))
+
+
+@pytest.mark.parametrize("grid_name", ["step1.05", "step1.02", "step1.01", "step1.005", "geom2048", "step1.01_20_20k",
+                                       "jitter1.01"])
+def test_oracle_curves_match_the_reference_run_on_other_grids(golden, grid_name):
+    """oracle.frequency_response smoothing and equalize against curves_edges.npz (the reference's FrequencyResponse run on
+    tests/golden/curves_inputs.py): curves whose first point the kink rule drops are extrapolated with the end piece of
+    the spline, as InterpolatedUnivariateSpline does.  1e-12 dB for smoothing and 1e-10 dB for the spline, relative to
+    max(1, max |want|): over the recorded curves SciPy's own rounding stays below both (tests/test_curves_edges.py)."""
+    import curves_inputs as ci
+    from oracle import frequency_response as ofr
+    z = golden("curves_edges")
+    f = ci.grid(grid_name)
+    assert tuple(z[f"{grid_name}/windows"]) == tuple(ofr.window_size(f, o) for o in ci.OCTAVES)
+    for k, (on, ot, fl, fu) in enumerate(ci.smoothing_pairs(grid_name)):
+        got = ofr.smoothen_fractional_octave(f, ci.walk(grid_name), on, ot, fl, fu)
+        assert _rel(got, z[f"{grid_name}/smooth{k}"]) <= 1e-12, (on, ot)
+    seen = dropped_first = 0
+    for c in ci.CURVES:
+        p, err = f"{grid_name}/{c}/", ci.curve(grid_name, c)
+        if p + "raises" in z:
+            with pytest.raises(ValueError, match="m > k"):
+                ofr.equalize(f, err, **ci.EQ_ARGS)
+        if p + "eq_raw" in z:
+            assert _rel(ofr.equalize(f, err, **ci.EQ_ARGS), z[p + "eq_raw"]) <= 1e-10, c
+            seen += 1
+            dropped_first += int(not z[p + "keep_raw"][0])
+        if p + "es" in z:
+            es = ofr.smoothen_heavy_light(f, err)
+            assert _rel(es, z[p + "es"]) <= 1e-12, c
+            assert _rel(ofr.equalize(f, es, **ci.EQ_ARGS), z[p + "eq_sm"]) <= 1e-10, c
+    assert seen >= 6 and (dropped_first >= 3 or ci.kink_half(grid_name) == 0)
