@@ -28,6 +28,7 @@
 #include "vbass_kernels.hip.h"
 #include "micdev_kernels.hip.h"
 #include "analysis_kernels.hip.h"
+#include "stft_kernels.hip.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -2088,6 +2089,109 @@ extern "C" int imp_energy_decay_db(imp_ctx* ctx, const double* x, const int64_t*
   BlockHold rows(ctx);
   if ((rc = upload_rows(ctx, "imp_energy_decay_db", x, sp.extent, rows))) return rc;
   return edc_impl<double>(ctx, "imp_energy_decay_db", (const double*)rows.p, off, len, B, floor_db, sp.total, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// K16 short-time spectra: the spectrogram and waterfall data of the plot stage
+// ------------------------------------------------------------------------------------------------
+static int stft_check(const char* who, const void* x, const int64_t* off, const int64_t* len, int64_t B, int64_t nfft, int64_t hop,
+                      double fs, int mode, const void* out, RowSpan* sp) {
+  if (!off || !len) return fail(IMP_ERR_INVALID, "%s: null argument", who);
+  if (B < 1 || B > 65535) return fail(IMP_ERR_INVALID, "%s: B = %lld rows (need 1 .. 65535)", who, (long long)B);
+  if (nfft < 2) return fail(IMP_ERR_INVALID, "%s: segment length nfft = %lld (need at least 2)", who, (long long)nfft);
+  if (hop < 1 || hop > nfft) return fail(IMP_ERR_INVALID, "%s: hop = %lld (need 1 .. nfft = %lld)", who, (long long)hop, (long long)nfft);
+  if (!(fs > 0.0) || std::isinf(fs)) return fail(IMP_ERR_INVALID, "%s: fs = %g", who, fs);
+  if (mode != IMP_STFT_PSD_DB && mode != IMP_STFT_MAGNITUDE) return fail(IMP_ERR_INVALID, "%s: mode %d", who, mode);
+  if (!stft_length_ok(nfft))
+    return fail(IMP_ERR_UNSUPPORTED, "%s: segment length nfft = %lld is not a product of the radices 2, 3, 5, 7, 11 that is at most "
+                "%d or splits into two such factors of at most %d", who, (long long)nfft, fft64_max_points(), fft64_max_points());
+  int rc = rows_check(who, off, len, B, (int64_t)1 << 26, sp);
+  if (rc) return rc;
+  int64_t total = 0;
+  for (int64_t b = 0; b < B; ++b)
+    if (len[b] >= nfft) total += (nfft / 2) * ((len[b] - (nfft - hop)) / hop);
+  if (total > ((int64_t)1 << 32)) return fail(IMP_ERR_UNSUPPORTED, "%s: %lld output values (limit 2^32)", who, (long long)total);
+  if ((sp->extent > 0 && !x) || (total > 0 && !out)) return fail(IMP_ERR_INVALID, "%s: null rows or output", who);
+  return IMP_OK;
+}
+
+template <class T>
+static int stft_impl(imp_ctx* ctx, const char* who, const T* d_x, const int64_t* off, const int64_t* len, int64_t B, int64_t nfft,
+                     int64_t hop, double fs, int mode, int out_is_f32, void* out) {
+  const int64_t nb = nfft / 2;
+  // scipy's scale 1 / (fs sum w^2) of the periodic Hann window, the sum in index order; its square root for the magnitudes
+  double w2 = 0.0;
+  for (int64_t n = 0; n < nfft; ++n) {
+    const double w = 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)n / (double)nfft);
+    w2 += w * w;
+  }
+  double scale = 1.0 / (fs * w2);
+  if (mode == IMP_STFT_MAGNITUDE) scale = std::sqrt(scale);
+  std::vector<imp::StftRow> rows((size_t)B);
+  int64_t n_xf = 0, total = 0, max_xf = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t S = len[b] >= nfft ? (len[b] - (nfft - hop)) / hop : 0;
+    rows[(size_t)b] = {off[b], len[b], total, n_xf, S};
+    n_xf += (S + 1) / 2;
+    max_xf = std::max(max_xf, (S + 1) / 2);
+    total += nb * S;
+  }
+  if (total == 0) return IMP_OK;
+  void* tab[1];
+  int rc = ctx_stage_tables(ctx, {{rows.data(), (size_t)B * sizeof(imp::StftRow)}}, tab);
+  if (rc) return rc;
+  // at most 128 MiB per transform buffer: more transforms go through in chunks
+  const int64_t cap = std::min<int64_t>(n_xf, std::max<int64_t>(1, ((int64_t)128 << 20) / (nfft * (int64_t)sizeof(double2))));
+  const size_t out_bytes = (size_t)total * (out_is_f32 ? sizeof(float) : sizeof(double));
+  BlockHold h_xf(ctx), h_za(ctx), h_zb(ctx), h_out(ctx);
+  if ((rc = h_xf.get((size_t)n_xf * sizeof(imp::StftXf))) || (rc = h_za.get((size_t)cap * (size_t)nfft * sizeof(double2))) ||
+      (rc = h_zb.get((size_t)cap * (size_t)nfft * sizeof(double2))) || (rc = h_out.get(out_bytes)))
+    return rc;
+  imp::StftXf* d_xf = (imp::StftXf*)h_xf.p;
+  hipStream_t s = ctx->stream;
+  hipLaunchKernelGGL(imp::stft_mean_kernel<T>, dim3((unsigned)max_xf, (unsigned)B), dim3(imp::kStftThreads), 0, s, d_x,
+                     (const imp::StftRow*)tab[0], (long long)nfft, (long long)hop, d_xf);
+  if (hipGetLastError() != hipSuccess) return fail(IMP_ERR_HIP, "%s: segment mean launch failed", who);
+  for (int64_t first = 0; first < n_xf; first += cap) {
+    const int64_t count = std::min(cap, n_xf - first);
+    double2* z = nullptr;
+    if ((rc = stft_spectra(ctx, d_x, d_xf + first, count, nfft, (double2*)h_za.p, (double2*)h_zb.p, &z))) return rc;
+    const dim3 grid((unsigned)((count + imp::kStftTileXf - 1) / imp::kStftTileXf), (unsigned)((nb + imp::kStftTileBins - 1) / imp::kStftTileBins));
+    if (out_is_f32)
+      hipLaunchKernelGGL(imp::stft_out_kernel<float>, grid, dim3(imp::kStftThreads), 0, s, (const double2*)z,
+                         (const imp::StftXf*)(d_xf + first), (long long)count, (long long)nfft, mode, scale, (float*)h_out.p);
+    else
+      hipLaunchKernelGGL(imp::stft_out_kernel<double>, grid, dim3(imp::kStftThreads), 0, s, (const double2*)z,
+                         (const imp::StftXf*)(d_xf + first), (long long)count, (long long)nfft, mode, scale, (double*)h_out.p);
+    if (hipGetLastError() != hipSuccess) return fail(IMP_ERR_HIP, "%s: epilogue launch failed", who);
+  }
+  const hipError_t e = hipMemcpyAsync(out, h_out.p, out_bytes, hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);
+  if (e != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+  if (e2 != hipSuccess) return fail(IMP_ERR_HIP, "%s: %s", who, hipGetErrorString(e2));
+  return IMP_OK;
+}
+
+extern "C" int imp_stft_db_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t B, int64_t nfft,
+                                  int64_t hop, double fs, int mode, int out_is_f32, void* out) {
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_stft_db_device: null ctx");
+  IMP_CTX_LOCK(ctx);
+  RowSpan sp;
+  int rc = stft_check("imp_stft_db_device", d_x, off, len, B, nfft, hop, fs, mode, out, &sp);
+  if (rc || (rc = ctx_bind(ctx))) return rc;
+  return stft_impl<float>(ctx, "imp_stft_db_device", d_x, off, len, B, nfft, hop, fs, mode, out_is_f32, out);
+}
+
+extern "C" int imp_stft_db(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t B, int64_t nfft, int64_t hop,
+                           double fs, int mode, int out_is_f32, void* out) {
+  if (!ctx) return fail(IMP_ERR_INVALID, "imp_stft_db: null ctx");
+  IMP_CTX_LOCK(ctx);
+  RowSpan sp;
+  int rc = stft_check("imp_stft_db", x, off, len, B, nfft, hop, fs, mode, out, &sp);
+  if (rc || (rc = ctx_bind(ctx))) return rc;
+  BlockHold rows(ctx);
+  if ((rc = upload_rows(ctx, "imp_stft_db", x, sp.extent, rows))) return rc;
+  return stft_impl<double>(ctx, "imp_stft_db", (const double*)rows.p, off, len, B, nfft, hop, fs, mode, out_is_f32, out);
 }
 
 // ------------------------------------------------------------------------------------------------

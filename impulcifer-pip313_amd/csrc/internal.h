@@ -120,3 +120,13 @@ int analysis_pair_spectra(imp_ctx* ctx, const float* d_x, const imp::AnPair* d_p
                           double2* b, double2** z);
 int analysis_pair_spectra(imp_ctx* ctx, const double* d_x, const imp::AnPair* d_pairs, int64_t count, int64_t nfft, double2* a,
                           double2* b, double2** z);
+
+// K16 (minphase.hip): spectra of count transforms of two windowed segments each (stft_kernels.hip.h); a, b: [count][nfft]
+// work buffers, *z the one that holds the result; stream ordered, no wait.  stft_length_ok: the tile plans hold nfft
+namespace imp { struct StftXf; }
+bool stft_length_ok(int64_t nfft);
+int fft64_max_points();
+int stft_spectra(imp_ctx* ctx, const float* d_x, const imp::StftXf* d_xf, int64_t count, int64_t nfft, double2* a, double2* b,
+                 double2** z);
+int stft_spectra(imp_ctx* ctx, const double* d_x, const imp::StftXf* d_xf, int64_t count, int64_t nfft, double2* a, double2* b,
+                 double2** z);

@@ -28,6 +28,8 @@
 #include "fft64.hip.h"
 #define IMP_ANALYSIS_PAIR_HOOK_ONLY
 #include "analysis_kernels.hip.h"
+#define IMP_STFT_HOOK_ONLY
+#include "stft_kernels.hip.h"
 
 typedef double2 cdbl;
 
@@ -1360,4 +1362,76 @@ int analysis_pair_spectra(imp_ctx* ctx, const float* d_x, const imp::AnPair* d_p
 int analysis_pair_spectra(imp_ctx* ctx, const double* d_x, const imp::AnPair* d_pairs, int64_t count, int64_t nfft, double2* a,
                           double2* b, double2** z) {
   return analysis_pair_spectra_t<double>(ctx, d_x, d_pairs, count, nfft, a, b, z);
+}
+
+// K16 (b): Z[b] = FFT_nfft of `count` transforms, each two windowed, mean-free segments as one complex signal
+// (stft_kernels.hip.h; StftIn forms them in the tile transform's load hook).  Only lengths the tile plans hold: a
+// segment length is fs / 10 at the rates of the path (2205 .. 19 200), and there is no other route.  a, b: [count][nfft]
+// each; *z: whichever of them holds the result.  Nothing here waits.
+int fft64_max_points() { return fft64::kMaxPoints; }
+bool stft_length_ok(int64_t nfft) { return nfft >= 2 && nfft <= ((int64_t)1 << 20) && fft64::make_plan((int)nfft, true).ok; }
+
+template <class T>
+static int stft_spectra_t(imp_ctx* ctx, const T* d_x, const imp::StftXf* d_xf, int64_t count, int64_t nfft, cdbl* a, cdbl* b,
+                          cdbl** z) {
+  if (!stft_length_ok(nfft)) return fail(IMP_ERR_UNSUPPORTED, "segment length %lld has no tile plan", (long long)nfft);
+  hipStream_t s = ctx->stream;
+  cdbl* roots = nullptr;
+  auto it = ctx->fft_roots.find((long long)nfft);
+  if (it != ctx->fft_roots.end()) {
+    roots = (cdbl*)it->second;
+  } else {
+    HIP_TRY(hipMalloc((void**)&roots, (size_t)nfft * sizeof(cdbl)));
+    hipLaunchKernelGGL(roots_kernel, dim3((unsigned)((nfft + 255) / 256)), dim3(256), 0, s, roots, (int)nfft);
+    HIP_TRY(hipGetLastError());
+    ctx->fft_roots[(long long)nfft] = roots;
+  }
+  const fft64::Plan pl = fft64::make_plan((int)nfft, true);
+  const imp::StftIn<T> in_op{d_x, d_xf, roots};
+  fft64::Args g = {};
+  g.roots = roots;
+  g.n_roots = (int)nfft;
+  g.dir = -1;
+  g.in_batch = g.out_batch = nfft;
+  g.in = a;                                                            // never read: the hook supplies every point
+  g.out = b;
+  g.nstages = (int)pl.r1.size();
+  for (int i = 0; i < g.nstages; ++i) g.radix[i] = pl.r1[(size_t)i];
+  g.P = pl.P1;
+  if (pl.P2 == 1) {
+    g.nvec = 1;
+    g.in_vec = g.out_vec = nfft;
+    g.in_elem = g.out_elem = 1;
+    *z = b;
+    return fft64_pass(ctx, g, count, in_op, fft64::NoOp{});
+  }
+  // the two passes of run_fft_ops: columns with the four-step twiddle into b, rows of b into a
+  g.nvec = pl.P2;
+  g.in_vec = g.out_vec = 1;
+  g.in_elem = g.out_elem = pl.P2;
+  g.twiddle = 1;
+  int rc = fft64_pass(ctx, g, count, in_op, fft64::NoOp{});
+  if (rc) return rc;
+  g.in = b;
+  g.out = a;
+  g.nvec = pl.P1;
+  g.P = pl.P2;
+  g.in_vec = pl.P2;
+  g.in_elem = 1;
+  g.out_vec = 1;
+  g.out_elem = pl.P1;
+  g.twiddle = 0;
+  g.nstages = (int)pl.r2.size();
+  for (int i = 0; i < g.nstages; ++i) g.radix[i] = pl.r2[(size_t)i];
+  *z = a;
+  return fft64_pass(ctx, g, count, fft64::NoOp{}, fft64::NoOp{});
+}
+
+int stft_spectra(imp_ctx* ctx, const float* d_x, const imp::StftXf* d_xf, int64_t count, int64_t nfft, double2* a, double2* b,
+                 double2** z) {
+  return stft_spectra_t<float>(ctx, d_x, d_xf, count, nfft, a, b, z);
+}
+int stft_spectra(imp_ctx* ctx, const double* d_x, const imp::StftXf* d_xf, int64_t count, int64_t nfft, double2* a, double2* b,
+                 double2** z) {
+  return stft_spectra_t<double>(ctx, d_x, d_xf, count, nfft, a, b, z);
 }

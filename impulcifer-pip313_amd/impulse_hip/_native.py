@@ -19,6 +19,9 @@ IMP_MODE_FULL = 1
 IMP_ERR_UNSUPPORTED = -3
 
 
+STFT_PSD_DB, STFT_MAGNITUDE = 0, 1          # mode of imp_stft_db*
+
+
 class NativeUnavailable(RuntimeError):
     """libimpulse_hip.so is missing or no MI355X (gfx950) device is usable."""
 
@@ -192,6 +195,8 @@ SIGNATURES = {
     "imp_binaural_metrics": (C.c_int, [_vp, _pd, _pi64, _pi64, _i64, _pi64, _pi64, _i64, _i64, _pd, _pd, _pi64, _pd]),
     "imp_energy_decay_db_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, C.c_double, _pd]),
     "imp_energy_decay_db": (C.c_int, [_vp, _pd, _pi64, _pi64, _i64, C.c_double, _pd]),
+    "imp_stft_db_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, _i64, _i64, C.c_double, C.c_int, C.c_int, _vp]),
+    "imp_stft_db": (C.c_int, [_vp, _pd, _pi64, _pi64, _i64, _i64, _i64, C.c_double, C.c_int, C.c_int, _vp]),
     "imp_apply_window": (C.c_int, [_vp, _pf, _pi64, _pi64, _i64, C.POINTER(WindowParams)]),
     "imp_apply_window_device": (C.c_int, [_vp, _vp, _pi64, _vp, _pi64, _pi64, _i64, C.POINTER(WindowParams)]),
     "imp_segset_create_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, C.POINTER(_vp), _pd]),
@@ -431,6 +436,33 @@ class Context:
             _check(self._lib.imp_energy_decay_db_device(self._h, _vp(int(dptr)), _ptr_i64(offs), _ptr_i64(lens), len(lens),
                                                         float(floor_db), out.ctypes.data_as(_pd)))
         return _unpack(out, lens)
+
+    def stft_db(self, rows, nfft, hop, fs, mode=STFT_PSD_DB, dtype=np.float64, dptr=None):
+        """K16 (imp_stft_db / imp_stft_db_device): per row the [nfft // 2, S] array scipy.signal.spectrogram gives with a
+        periodic Hann window of nfft samples and noverlap = nfft - hop, bin 0 dropped: 10 log10(|psd| + 1e-9) for
+        STFT_PSD_DB, the scaled magnitudes for STFT_MAGNITUDE; S = (len - noverlap) // hop, 0 for a row shorter than nfft.
+        dtype float64 or float32.  rows as in binaural_metrics."""
+        nfft, hop = int(nfft), int(hop)
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError(f"stft_db: dtype {dtype} (need float64 or float32)")
+        if dptr is None:
+            flat, offs, lens = _pack(rows, np.float64)
+        else:
+            offs = np.ascontiguousarray(rows[0], dtype=np.int64)
+            lens = np.ascontiguousarray(rows[1], dtype=np.int64)
+        if nfft < 1 or hop < 1:
+            raise ValueError(f"stft_db: nfft = {nfft}, hop = {hop}")
+        segs = [int(n - (nfft - hop)) // hop if n >= nfft else 0 for n in lens]
+        sizes = [(nfft // 2) * s for s in segs]
+        out = np.zeros(max(sum(sizes), 1), dtype=dtype)
+        tail = (len(lens), nfft, hop, float(fs), int(mode), int(dtype == np.dtype(np.float32)), _vp(out.ctypes.data))
+        if dptr is None:
+            _check(self._lib.imp_stft_db(self._h, flat.ctypes.data_as(_pd), _ptr_i64(offs), _ptr_i64(lens), *tail))
+        else:
+            _check(self._lib.imp_stft_db_device(self._h, _vp(int(dptr)), _ptr_i64(offs), _ptr_i64(lens), *tail))
+        ends = np.cumsum(sizes)
+        return [out[int(e - n):int(e)].reshape(nfft // 2, s) for e, n, s in zip(ends, sizes, segs)]
 
     # ---- device-resident rows (fp32 at dptr + off[b], len[b] samples) ---------------------------
     @staticmethod

@@ -447,6 +447,21 @@ class HRIR(object):
                 out[sp]["edc_db"] = {"left": r["edc_db"][0], "right": r["edc_db"][1]}
         return out
 
+    def spectrograms(self, recordings=None, f_res=10, n_segments=200, dtype=np.float64):
+        """The spectrogram data of every channel, {speaker: {side: (f, t, z_db) or None}}: what the reference's
+        ImpulseResponse.plot_spectrogram computes per channel (the reference plot mixin impulse_response_plotter.py:114-293), for all
+        channels in one K16 batch (plot_data.spectrograms).  recordings: the reference's recordings[speaker][side] mapping
+        (core/pipeline.py:754-781: arrays, or device rows as parallel_workers.process_plot_batch leaves them), default each
+        response's own .recording.  Device rows are read where they are."""
+        from .plot_data import spectrograms
+        keys = [(sp, sd) for sp, pair in self.irs.items() for sd in pair]
+        recs = [self.irs[sp][sd].recording if recordings is None else recordings.get(sp, {}).get(sd) for sp, sd in keys]
+        res = spectrograms(recs, self.fs, f_res=f_res, n_segments=n_segments, dtype=dtype)
+        out = {}
+        for (sp, sd), r in zip(keys, res):
+            out.setdefault(sp, {})[sd] = r
+        return out
+
     # ---- cropping ------------------------------------------------------------------------
     def _all_irs(self):
         return [(sp, sd, ir) for sp, pair in self.irs.items() for sd, ir in pair.items()]

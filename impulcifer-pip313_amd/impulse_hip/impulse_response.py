@@ -209,6 +209,23 @@ class ImpulseResponse(object):
     def convolve(self, x):
         return fir_convolve_full(x, self.data)
 
+    def spectrogram_data(self, recording=None, f_res=10, n_segments=200):
+        """(f, t, z_db) of the recorded sweep's spectrogram as the reference's plot_spectrogram draws it
+        (the reference plot mixin impulse_response_plotter.py:114-293), computed on the device (K16, plot_data.spectrograms); None
+        where the reference draws nothing.  recording: an array or a device-resident response, default self.recording."""
+        from .plot_data import spectrograms
+        if recording is None:
+            recording = self.recording
+        if recording is None:
+            return None
+        return spectrograms([recording], self.fs, f_res=f_res, n_segments=n_segments)[0]
+
+    def waterfall_data(self):
+        """(t_ms, log10_f, z_db) of the decay waterfall as the reference's plot_waterfall draws it (:459-609); the
+        short-time magnitudes on the device (K16), a device-resident response is read in place."""
+        from .plot_data import waterfalls
+        return waterfalls([self], self.fs)[0]
+
     def decay_adjustment_params(self, target):
         return decay.decay_adjustment_params(self.data, self.fs, target)
 

@@ -9,6 +9,40 @@ def process_plot_worker(args):
     return (speaker, side, fir_convolve_full(test_signal, ir_data))
 
 
+def process_plot_batch(tasks):
+    """[(speaker, side, ir_data, test_signal, fs)] -> [(speaker, side, recording)] as process_plot_worker gives them, for all
+    channels of a measurement in ONE K5 launch group, and the recordings stay on the device: each is an ImpulseResponse
+    whose samples are a row of one device block (np.asarray(r.data) brings one to the host), which
+    HRIR.spectrograms(recordings=...) and plot_data.spectrograms read in place.  The channels must share the test signal's
+    length and the response length (the reference's post-processing plot stage, core/pipeline.py:754-781: every response
+    is cropped to one length by then)."""
+    import numpy as np
+    from . import _native
+    from .device_rows import DeviceBlock, Row
+    from .impulse_response import ImpulseResponse, _k5_plans
+    tasks = list(tasks)
+    if not tasks:
+        return []
+    sigs = [np.asarray(t[3], dtype=np.float64).ravel() for t in tasks]
+    taps = [np.asarray(t[2], dtype=np.float64).ravel() for t in tasks]
+    n, k = len(sigs[0]), len(taps[0])
+    if n == 0 or k == 0 or any(len(x) != n for x in sigs) or any(len(h) != k for h in taps):
+        raise ValueError("process_plot_batch: the channels need one test signal length and one response length, both non-zero")
+    ctx = _native.default_context()
+    B = len(tasks)
+    in_pitch, out_pitch = (n + 63) // 64 * 64, (n + k - 1 + 63) // 64 * 64
+    src = DeviceBlock(ctx, B * in_pitch)
+    staged = np.zeros((B, in_pitch), dtype=np.float32)
+    for i, x in enumerate(sigs):
+        staged[i, :n] = x
+    ctx.h2d(src.ptr, staged)
+    dst = DeviceBlock(ctx, B * out_pitch)
+    out_len = _k5_plans.run_device(src.ptr, B, in_pitch, n, np.stack(taps), dst.ptr, out_pitch)
+    ctx.synchronize()                                      # src may go once the launch group has run
+    src.close()
+    return [(t[0], t[1], ImpulseResponse.on_device(Row(dst, i * out_pitch, out_len), t[4])) for i, t in enumerate(tasks)]
+
+
 def process_decay_worker(args):
     """(speaker, side, ir_data, fs, target) -> (speaker, side, decay-adjusted copy of ir_data)."""
     speaker, side, ir_data, fs, target = args

@@ -404,6 +404,30 @@ int imp_energy_decay_db_device(imp_ctx* ctx, const float* d_x, const int64_t* of
 int imp_energy_decay_db(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t B, double floor_db,
                         double* out);
 
+/* ---- K16: short-time spectra of rows, fp64: spectrogram and waterfall data of the plot stage -------------
+ * What ImpulseResponse.plot() computes before it draws (core/plotting/impulse_response_plotter.py:114-293 plot_spectrogram on
+ * every channel's recorded sweep and, after processing, on convolve(test_signal, ir.data), core/pipeline.py:754-781;
+ * :459-609 plot_waterfall on every response): scipy.signal.spectrogram(x, fs, window=get_window("hann", nfft), nperseg=nfft,
+ * noverlap=nfft - hop, mode=...) of B rows with one geometry (nfft, hop), 1 <= hop <= nfft.
+ * Row b has S_b = (len[b] - (nfft - hop)) / hop segments x[s hop .. s hop + nfft), none when len[b] < nfft.  Every segment
+ * loses its own mean (scipy's detrend="constant"), is multiplied by the periodic Hann window 0.5 - 0.5 cos(2 pi n / nfft) and
+ * transformed; bin 0 is dropped.
+ *   mode IMP_STFT_PSD_DB (:215-256):    10 log10(|p| + 1e-9), p = |X|^2 / (fs sum w^2), doubled except at the Nyquist bin of an
+ *                                       even nfft
+ *   mode IMP_STFT_MAGNITUDE (:508-530): |X| sqrt(1 / (fs sum w^2))
+ * out: per row [nfft / 2][S_b], frequency-major as the reference's z, the rows packed one after the other (sum of
+ * (nfft / 2) S_b values); double, or float with out_is_f32 (the double values rounded once).
+ * nfft must be a length the fp64 tile transform holds: a product of the radices 2, 3, 5, 7, 11 that is at most 1024 or
+ * splits into two such factors of at most 1024 (fs / 10 at every rate from 22.05 k to 192 k does); anything else is
+ * IMP_ERR_UNSUPPORTED.  A row's result does not depend on the other rows of the call.  Synchronous.
+ * imp_stft_db_device: fp32 device rows at d_x + off[b];  imp_stft_db: fp64 host rows at x + off[b]. */
+#define IMP_STFT_PSD_DB 0
+#define IMP_STFT_MAGNITUDE 1
+int imp_stft_db_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t B, int64_t nfft, int64_t hop,
+                       double fs, int mode, int out_is_f32, void* out);
+int imp_stft_db(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t B, int64_t nfft, int64_t hop, double fs,
+                int mode, int out_is_f32, void* out);
+
 /* ---- K6: minimum-phase FIR design, batched, fp64 -----------------------------------------------
  * Tail of FrequencyResponse.minimum_phase_impulse_response (autoeq/frequency_response.py:676-680),
  * called per channel by core/parallel_workers.py:129:
