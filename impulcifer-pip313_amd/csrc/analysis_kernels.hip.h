@@ -15,17 +15,14 @@
 //                            conflict) and adds sum_n l[n + lag] r[n] over the tile in sample order; the tile's sum l^2 and
 //                            sum r^2 by a fixed tree.  iacf_finish_kernel, grid (pairs): the tiles in tile order, divided by
 //                            sqrt(E_l E_r); the first index of max |iacf| among the lags scipy's 'full' mode has.
-//   (c) EDC                  edc_kernel<Sample>, grid (rows): block_scan (ir_kernels.hip.h) over the squares from the row's
+//   (c) EDC                  edc_kernel<Sample>, grid (rows): block_scan (block_scan.hip.h) over the squares from the row's
 //                            end, then 10 log10(e / (e[0] + 1e-12) + 1e-12), or floor_db when e[0] <= 1e-12.
 // fp64 throughout; Sample = float rows are widened exactly on load.  Contraction is off except for the explicit fma of the
 // lag sums.  No scratch.
-// minphase.hip, which owns the transform, includes this header with IMP_ANALYSIS_PAIR_HOOK_ONLY for the load hook alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#ifndef IMP_ANALYSIS_PAIR_HOOK_ONLY
-#include "ir_kernels.hip.h"
-#endif
+#include "block_scan.hip.h"
 
 namespace imp {
 
@@ -58,7 +55,6 @@ __global__ __launch_bounds__(kAnThreads) void pair_pack_kernel(const T* __restri
   z[(long long)blockIdx.y * nfft + e] = PairIn<T>{x, pairs}(make_double2(0.0, 0.0), blockIdx.y, e);
 }
 
-#ifndef IMP_ANALYSIS_PAIR_HOOK_ONLY
 // bins: [pairs][bands][2] = (k0, k1), 0 <= k0 <= k1 <= nfft / 2 + 1 checked by the host; out: [pairs][bands][4]
 static __global__ __launch_bounds__(kAnThreads) void band_cross_kernel(const double2* __restrict__ z, long long nfft,
                                                                        const long long* __restrict__ bins, int bands,
@@ -250,7 +246,5 @@ __global__ __launch_bounds__(kDecayThreads) void edc_kernel(const T* __restrict_
   const double den = total + 1e-12;
   for (long long i = threadIdx.x; i < n; i += kDecayThreads) o[i] = 10.0 * log10(sc[n - 1 - i] / den + 1e-12);
 }
-
-#endif  // IMP_ANALYSIS_PAIR_HOOK_ONLY
 
 }  // namespace imp

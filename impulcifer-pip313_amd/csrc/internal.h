@@ -57,7 +57,7 @@ struct imp_ctx {
   // through the chirp-z transform, the cross-check of the direct transform that smooth lengths take
   std::map<long long, struct MagPlan*> magnitude_plans;
   bool k2_bluestein_only = false;
-  // fp64 roots of unity on the device, keyed by transform length (filter-spectrum preparation)
+  // fp64 roots of unity made on the device, keyed by transform length (fft64_host.hip.h ctx_fft_roots)
   std::map<long long, void*> fft_roots;
   // kernels whose dynamic-LDS opt-in (hipFuncAttributeMaxDynamicSharedMemorySize) has been made ON THIS DEVICE:
   // the attribute is per device, so it is tracked per context, under the context lock
@@ -92,41 +92,23 @@ int ctx_kernel_lds(imp_ctx* ctx, const void* kernel, size_t bytes);
 int ctx_bind(imp_ctx* ctx);
 // a new non-blocking stream of the context's device
 int ctx_new_stream(imp_ctx* ctx, hipStream_t* out);
-void minphase_plans_destroy(imp_ctx* ctx);
-void magnitude_plans_destroy(imp_ctx* ctx);
-void fft_roots_destroy(imp_ctx* ctx);
+void minphase_plans_destroy(imp_ctx* ctx);       // minphase.hip
+void magnitude_plans_destroy(imp_ctx* ctx);      // magnitude.hip
+void fft_roots_destroy(imp_ctx* ctx);            // spectra.hip
 // alpha/beta planes of `n_filters` real filters (host fp64, row pitch filter_ld) for circular length
 // 2 Nc, computed in fp64 ON THE DEVICE and rounded once to fp32 into d_ab[n_filters][N1*4096]
-// (register order of the row pass).  minphase.hip, next to the fp64 Stockham FFT it uses.
+// (register order of the row pass).  spectra.hip.
 int spectrum_alpha_beta_device(imp_ctx* ctx, const double* filters, int64_t M, int64_t n_filters, int64_t filter_ld,
                                int64_t Nc, int N1, float4* d_ab, bool filters_on_device = false);
 // Pair-mode spectrum (conv_kernels.hip.h rows_single_kernel): H[k] / Nc of ONE real filter zero-padded to the circular
 // length Nc = N1 * 4096 samples, all Nc bins, fp64 on the device, rounded once to fp32 into d_hs[N1][4096] in the row
-// pass's register order.
+// pass's register order.  spectra.hip.
 int spectrum_pair_device(imp_ctx* ctx, const double* filter, int64_t M, int64_t Nc, int N1, cf* d_hs);
 
-// K2 of imp_slice (minphase.hip): maxima of the ear sums' magnitude responses for row lengths that live on the device
+// K2 of imp_slice (magnitude.hip): maxima of the ear sums' magnitude responses for row lengths that live on the device
 struct SliceNorm;
 int slice_norm_create(imp_ctx* ctx, int64_t n_max, int64_t m_cap, SliceNorm** out);
 void slice_norm_destroy(SliceNorm* p);
 int64_t slice_norm_mfft(const SliceNorm* p);
 int slice_norm_run(imp_ctx* ctx, SliceNorm* p, const float* d_rows, int64_t pitch, int rows_per_meas, const long long* d_n,
                    int64_t M, double* d_peak_db);
-
-// K15 (a) (minphase.hip, next to the fp64 transform): spectra of count pairs z = x_L + i x_R zero padded to nfft; a, b:
-// [count][nfft] work buffers, *z the one that holds the result; stream ordered, no wait
-namespace imp { struct AnPair; }
-int analysis_pair_spectra(imp_ctx* ctx, const float* d_x, const imp::AnPair* d_pairs, int64_t count, int64_t nfft, double2* a,
-                          double2* b, double2** z);
-int analysis_pair_spectra(imp_ctx* ctx, const double* d_x, const imp::AnPair* d_pairs, int64_t count, int64_t nfft, double2* a,
-                          double2* b, double2** z);
-
-// K16 (minphase.hip): spectra of count transforms of two windowed segments each (stft_kernels.hip.h); a, b: [count][nfft]
-// work buffers, *z the one that holds the result; stream ordered, no wait.  stft_length_ok: the tile plans hold nfft
-namespace imp { struct StftXf; }
-bool stft_length_ok(int64_t nfft);
-int fft64_max_points();
-int stft_spectra(imp_ctx* ctx, const float* d_x, const imp::StftXf* d_xf, int64_t count, int64_t nfft, double2* a, double2* b,
-                 double2** z);
-int stft_spectra(imp_ctx* ctx, const double* d_x, const imp::StftXf* d_xf, int64_t count, int64_t nfft, double2* a, double2* b,
-                 double2** z);

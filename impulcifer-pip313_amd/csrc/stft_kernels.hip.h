@@ -19,7 +19,6 @@
 //                                  the bins, the writes along the segments, both contiguous.
 // fp64 throughout; Sample = float rows are widened exactly on load, Out = float is rounded once on store.  No atomics, no
 // scratch, contraction off.  A row's values depend on that row alone.
-// minphase.hip, which owns the transform, includes this header with IMP_STFT_HOOK_ONLY for the record and the load hook.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,7 +59,6 @@ struct StftIn {
   }
 };
 
-#ifndef IMP_STFT_HOOK_ONLY
 template <class T>
 __global__ __launch_bounds__(kStftThreads) void stft_mean_kernel(const T* __restrict__ x, const StftRow* __restrict__ rows,
                                                                  long long nfft, long long hop, StftXf* __restrict__ xf) {
@@ -152,6 +150,4 @@ __global__ __launch_bounds__(kStftThreads) void stft_out_kernel(const double2* _
     }
   }
 }
-#endif  // IMP_STFT_HOOK_ONLY
-
 }  // namespace imp

@@ -832,6 +832,45 @@ def test_magnitude_direct_transform_equals_bluestein(gpu_ctx, monkeypatch):
         chirp.close()
 
 
+@pytest.mark.parametrize("n", [1, 2, 7, 16386])
+def test_magnitude_peak_only_equals_max_of_full_spectra(gpu_ctx, n):
+    """HRIR.normalize's peak-only path (rows_max_kernel after the transform) returns, bit for bit, np.max over the spectra of
+    the full path, for two groups of two ragged fp32 device rows.  n = 1: one bin, chirp-z with a 4-point convolution;
+    n = 2: the direct transform; n = 7: chirp-z, odd; n = 16 386 = 2 * 3 * 2731: chirp-z with 32 768 points, and its 8 193
+    bins are one more than the kernel's first block of 8 x 1024 loads.  A NaN sample makes its group's peak NaN, a group of
+    all-zero rows gives -inf (what np.max returns), the other group stays finite."""
+    from impulse_hip.device_rows import DeviceBlock, Row, span
+    rng = np.random.default_rng(0xD16 + n)
+    lens = [n, n - n // 3, n // 2, n]                                       # ragged; groups 0, 1, 0, 1
+    pitch = n + 3
+    plain = np.zeros((4, pitch), dtype=np.float32)
+    for i, ln in enumerate(lens):
+        plain[i, :ln] = rng.standard_normal(ln).astype(np.float32)
+    with_nan = plain.copy()
+    with_nan[0, n - 1] = np.nan                                             # group 0, past the end of its shorter row
+    zero_group = plain.copy()
+    zero_group[1] = zero_group[3] = 0.0                                     # group 1
+    blk = DeviceBlock(gpu_ctx, 4 * pitch)
+    try:
+        base, offs, lens_ = span([Row(blk, i * pitch, lens[i]) for i in range(4)])
+        for kind, rows in (("plain", plain), ("nan", with_nan), ("zero", zero_group)):
+            gpu_ctx.h2d(blk.ptr, rows)
+            with np.errstate(invalid="ignore"):
+                full = gpu_ctx.magnitude_db_sum_device(base, offs, lens_, [0, 1, 0, 1], 2, n)
+                peak = gpu_ctx.magnitude_db_sum_peak_device(base, offs, lens_, [0, 1, 0, 1], 2, n)
+                want = np.max(full, axis=1)
+            assert full.shape == (2, (n + 1) // 2) and peak.shape == (2,)
+            assert np.array_equal(peak, want, equal_nan=True), (n, kind, peak, want)
+            if kind == "plain":
+                assert np.all(np.isfinite(peak)), (n, peak)
+            elif kind == "nan":
+                assert np.isnan(peak[0]) and np.isfinite(peak[1]), (n, peak)
+            else:
+                assert np.isfinite(peak[0]) and np.isneginf(peak[1]), (n, peak)
+    finally:
+        blk.close()
+
+
 # ------------------------------------------------------------------------------------------------
 # alignment / shift (next-tier row f1; host-side correlations): the reference's own assertions
 # (tests/test_dsp_stages.py:105-166)
