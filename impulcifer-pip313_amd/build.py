@@ -10,9 +10,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libimpulse_hip.so")
-SOURCES = ["impulse_hip.hip", "analysis.hip", "minphase.hip", "magnitude.hip", "spectra.hip", "curves.hip", "comm.hip"]
+SOURCES = ["impulse_hip.hip", "analysis.hip", "minphase.hip", "magnitude.hip", "spectra.hip", "curves.hip", "resample.hip",
+           "comm.hip"]
 HEADERS = ["conv_kernels.hip.h", "fft_regs.hip.h", "ir_kernels.hip.h", "decay_kernels.hip.h",
            "slice_kernels.hip.h", "vbass_kernels.hip.h", "micdev_kernels.hip.h", "analysis_kernels.hip.h", "stft_kernels.hip.h",
+           "resample_kernels.hip.h",
            "slice_host.hip.inc", "fft64.hip.h", "fft64_host.hip.h", "block_scan.hip.h", "ragged_rows.h", "internal.h",
            os.path.join("..", "..", "include", "impulse_hip.h")]
 

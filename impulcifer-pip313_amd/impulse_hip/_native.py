@@ -16,6 +16,7 @@ _DEFAULT_LIB = os.path.normpath(os.path.join(_HERE, "..", "csrc", "libimpulse_hi
 
 IMP_MODE_SAME = 0
 IMP_MODE_FULL = 1
+IMP_ERR_INVALID = -1
 IMP_ERR_UNSUPPORTED = -3
 
 
@@ -197,6 +198,9 @@ SIGNATURES = {
     "imp_energy_decay_db": (C.c_int, [_vp, _pd, _pi64, _pi64, _i64, C.c_double, _pd]),
     "imp_stft_db_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, _i64, _i64, C.c_double, C.c_int, C.c_int, _vp]),
     "imp_stft_db": (C.c_int, [_vp, _pd, _pi64, _pi64, _i64, _i64, _i64, C.c_double, C.c_int, C.c_int, _vp]),
+    "imp_resample_poly_len": (C.c_int, [_i64, _i64, _i64, _pi64]),
+    "imp_resample_poly_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, _i64, _i64, _pd, _i64, _vp, _pi64]),
+    "imp_resample_poly": (C.c_int, [_vp, _pd, _pi64, _pi64, _i64, _i64, _i64, _pd, _i64, _pd, _pi64]),
     "imp_apply_window": (C.c_int, [_vp, _pf, _pi64, _pi64, _i64, C.POINTER(WindowParams)]),
     "imp_apply_window_device": (C.c_int, [_vp, _vp, _pi64, _vp, _pi64, _pi64, _i64, C.POINTER(WindowParams)]),
     "imp_segset_create_device": (C.c_int, [_vp, _vp, _pi64, _pi64, _i64, C.POINTER(_vp), _pd]),
@@ -463,6 +467,31 @@ class Context:
             _check(self._lib.imp_stft_db_device(self._h, _vp(int(dptr)), _ptr_i64(offs), _ptr_i64(lens), *tail))
         ends = np.cumsum(sizes)
         return [out[int(e - n):int(e)].reshape(nfft // 2, s) for e, n, s in zip(ends, sizes, segs)]
+
+    def resample_poly(self, rows, up, down, taps, dptr=None, d_dst=None, dst_off=None):
+        """K17 (imp_resample_poly / imp_resample_poly_device): scipy.signal.resample_poly(row, up, down, window=taps) of every
+        row.  rows: host 1-D arrays (fp64 upload; returns a list of fp64 arrays), or with dptr the (offsets, lengths) of fp32
+        device rows at dptr, whose results go to d_dst + dst_off[b] as fp32 in stream order (returns their lengths)."""
+        taps = np.ascontiguousarray(taps, dtype=np.float64)
+        if taps.ndim != 1:
+            raise ValueError(f"resample_poly: taps of shape {taps.shape} (need one dimension)")
+        up, down = int(up), int(down)
+        if dptr is None:
+            flat, offs, lens = _pack(rows, np.float64)
+        else:
+            offs = np.ascontiguousarray(rows[0], dtype=np.int64)
+            lens = np.ascontiguousarray(rows[1], dtype=np.int64)
+        n_out = np.array([resample_poly_len(n, up, down) for n in lens], dtype=np.int64)
+        if dptr is None:
+            pos = np.cumsum(n_out) - n_out
+            out = np.zeros(max(int(n_out.sum()), 1), dtype=np.float64)
+            _check(self._lib.imp_resample_poly(self._h, flat.ctypes.data_as(_pd), _ptr_i64(offs), _ptr_i64(lens), len(lens), up, down,
+                                               taps.ctypes.data_as(_pd), len(taps), out.ctypes.data_as(_pd), _ptr_i64(pos)))
+            return _unpack(out, n_out)
+        dst_off = np.ascontiguousarray(dst_off, dtype=np.int64)
+        _check(self._lib.imp_resample_poly_device(self._h, _vp(int(dptr)), _ptr_i64(offs), _ptr_i64(lens), len(lens), up, down,
+                                                  taps.ctypes.data_as(_pd), len(taps), _vp(int(d_dst)), _ptr_i64(dst_off)))
+        return n_out
 
     # ---- device-resident rows (fp32 at dptr + off[b], len[b] samples) ---------------------------
     @staticmethod
@@ -1434,6 +1463,13 @@ class ConvPlan:
             self.close()
         except Exception:
             pass
+
+
+def resample_poly_len(n_in, up, down):
+    """len(scipy.signal.resample_poly(np.zeros(n_in), up, down)) = ceil(n_in up / down) with the ratio reduced; needs no GPU."""
+    n = C.c_int64(0)
+    _check(load_library().imp_resample_poly_len(int(n_in), int(up), int(down), C.byref(n)))
+    return n.value
 
 
 def plan_geometry(M, L, mode="same"):

@@ -428,6 +428,28 @@ int imp_stft_db_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const
 int imp_stft_db(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t B, int64_t nfft, int64_t hop, double fs,
                 int mode, int out_is_f32, void* out);
 
+/* ---- K17: rational resampling of rows, fp64 ---------------------------------------------------------------
+ * ImpulseResponse.resample (core/impulse_response.py:121-124), called per response by HRIR.resample (core/hrir.py:890-919)
+ * in the --fs stage: nnresample.resample(x, up, down) = scipy.signal.resample_poly(x, up, down, window=taps) with taps from
+ * nnresample.compute_filt.  The filter is designed on the host (impulse_hip/resampling.py kaiser_null_filter, or the
+ * caller's own) and handed in; this is the polyphase arithmetic.  With up / down reduced by their gcd, half = (L - 1) / 2
+ * and n_out = ceil(len[b] up / down), row b becomes
+ *   y[m] = up * sum_k taps[m down + half - k up] x[k]     0 <= m < n_out, 0 <= k < len[b], tap index in [0, L)
+ * (SciPy's padding and trimming, collapsed); up == down after reduction gives a copy of the row.  Products and sums are
+ * fp64, and the summation order of an output depends on (m, up, down, L) alone: a row's result does not depend on the other
+ * rows of the call, its place among them or the launch.  taps is a HOST table of L values in both entry points.
+ * IMP_ERR_INVALID for up <= 0, down <= 0, a negative length or offset, L < 1 or a null table; IMP_ERR_UNSUPPORTED for
+ * L > 65536, B > 65535 or a row with len up + down + L >= 2^62.  A zero-length row gives a zero-length result; B = 0 succeeds.
+ * imp_resample_poly_len: n_out of a row of n_in samples; needs no GPU.
+ * imp_resample_poly_device: fp32 device rows at d_x + off[b], results rounded once to fp32 at d_dst + dst_off[b] (n_out
+ *   samples each, not the source rows); asynchronous on the context's stream.
+ * imp_resample_poly: fp64 host rows at x + off[b], fp64 results at out + out_off[b]; synchronous. */
+int imp_resample_poly_len(int64_t n_in, int64_t up, int64_t down, int64_t* n_out);
+int imp_resample_poly_device(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t B, int64_t up,
+                             int64_t down, const double* taps, int64_t L, float* d_dst, const int64_t* dst_off);
+int imp_resample_poly(imp_ctx* ctx, const double* x, const int64_t* off, const int64_t* len, int64_t B, int64_t up, int64_t down,
+                      const double* taps, int64_t L, double* out, const int64_t* out_off);
+
 /* ---- K6: minimum-phase FIR design, batched, fp64 -----------------------------------------------
  * Tail of FrequencyResponse.minimum_phase_impulse_response (autoeq/frequency_response.py:676-680),
  * called per channel by core/parallel_workers.py:129:
