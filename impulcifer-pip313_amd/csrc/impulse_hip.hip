@@ -1512,6 +1512,66 @@ extern "C" int imp_plan_debug_run_stage(imp_plan* p, const float* x, int64_t B, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Launch sequences that the staged entry points below and the resident slice (slice_host.hip.inc) share
+// ------------------------------------------------------------------------------------------------
+// grid of the row-parallel kernels (apply_window*, shift_rows): up to 256 blocks a row, one per 1024 samples of the longest
+static dim3 rows_grid(int64_t n_max, int64_t B) {
+  return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (n_max + 1023) / 1024)), (unsigned)B);
+}
+
+// K4/K8 from one set of device rows into another (or in place); n_max: the longest row
+static int launch_window_copy(hipStream_t st, const float* src, const int64_t* src_off, float* dst, const int64_t* dst_off,
+                              const int64_t* len, const imp::WindowParams* par, int64_t n_max, int64_t B) {
+  hipLaunchKernelGGL(imp::apply_window_copy_kernel, rows_grid(n_max, B), dim3(256), 0, st, src, src_off, dst, dst_off, len, par);
+  HIP_TRY(hipGetLastError());
+  return IMP_OK;
+}
+
+// K3: first peaks of B device rows into d_res (and d_peaks_out, optional).  Plain form: the chunk pass over the rows
+// (d_chunk: [B][chunks]), then the search.  Tile form (tile_max given): K1's pass C left the maxima per column tile
+// ([B][tiles][chunks], the rows start `shift` samples into their first chunk) and there is no chunk pass.
+static int launch_first_peaks(hipStream_t st, const float* x, const int64_t* d_off, const int64_t* d_len, int64_t B, unsigned* d_chunk,
+                              int64_t chunks, imp::RowPeak* d_res, double peak_height, long long* d_peaks_out, int64_t shift = 0,
+                              const unsigned* tile_max = nullptr, int tiles = 0) {
+  if (!tile_max)
+    hipLaunchKernelGGL(imp::row_chunk_max_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, st, x, d_off, d_len, shift, d_chunk,
+                       chunks);
+  hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)B), dim3(imp::kPeakThreads), 0, st, x, d_off, d_len, shift,
+                     tile_max, tiles, tile_max ? (const unsigned*)nullptr : (const unsigned*)d_chunk, chunks, d_res, peak_height,
+                     d_peaks_out);
+  HIP_TRY(hipGetLastError());
+  return IMP_OK;
+}
+
+// K7c after the peaks: the Lundeby knee search of B device rows (decay_kernels.hip.h), no host round trip in between
+constexpr int kKneeMeanPitch = imp::kKneeMaxWindows + 1;   // doubles of d_means per row
+struct KneeScratch {
+  const imp::RowPeak* d_res;         // [B] in: launch_first_peaks of the same rows
+  unsigned long long* d_max;         // [B] span maxima bits
+  imp::KneeRow* d_knee;              // [B] search state, the result
+  double* d_means;                   // [B][kKneeMeanPitch] window means
+};
+// span_len_max: the longest row (the analysed span is at most int(2 fs) of it)
+static int launch_knee_search(hipStream_t st, const float* x, const int64_t* d_off, const int64_t* d_len, int64_t B,
+                              int64_t span_len_max, double fs, const KneeScratch& k) {
+  const int64_t two_fs = (int64_t)(2 * fs);               // int(2 * fs), core/decay.py:84
+  const int64_t span_max = std::max<int64_t>(1, std::min(two_fs, span_len_max));
+  const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(64, (span_max + 8191) / 8192));
+  const dim3 rows((unsigned)B), block(256);
+  hipLaunchKernelGGL(imp::knee_span_kernel, rows, dim3(64), 0, st, k.d_res, d_off, d_len, (long long)two_fs, fs, k.d_knee, k.d_max);
+  hipLaunchKernelGGL(imp::knee_maxabs_kernel, dim3((unsigned)bpr, (unsigned)B), block, 0, st, x, (const imp::KneeRow*)k.d_knee, k.d_max);
+  hipLaunchKernelGGL(imp::knee_windows_kernel, dim3(imp::kKneeRound1, (unsigned)B), block, 0, st, (const imp::KneeRow*)k.d_knee, x,
+                     (const unsigned long long*)k.d_max, k.d_means, kKneeMeanPitch, 1);
+  hipLaunchKernelGGL(imp::knee_stage1_kernel, rows, dim3(64), 0, st, k.d_knee, (const double*)k.d_means, kKneeMeanPitch, fs);
+  hipLaunchKernelGGL(imp::knee_windows_kernel, dim3(64, (unsigned)B), block, 0, st, (const imp::KneeRow*)k.d_knee, x,
+                     (const unsigned long long*)k.d_max, k.d_means, kKneeMeanPitch, 0);
+  hipLaunchKernelGGL(imp::knee_stage2_kernel, rows, block, 0, st, k.d_knee, (const double*)k.d_means, kKneeMeanPitch, x,
+                     (const unsigned long long*)k.d_max, fs);
+  HIP_TRY(hipGetLastError());
+  return IMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // K3 peak index, K4/K8 windows (ragged batches)
 // ------------------------------------------------------------------------------------------------
 static int peak_index_impl(imp_ctx* ctx, const float* d_x, const int64_t* off, const int64_t* len, int64_t B, int64_t maxlen,
@@ -1532,12 +1592,7 @@ static int peak_index_impl(imp_ctx* ctx, const float* d_x, const int64_t* off, c
   void* tab[2];
   if ((rc = ctx_stage_tables(ctx, {{off, meta}, {len, meta}}, tab))) return rc;
   const int64_t *d_off = (const int64_t*)tab[0], *d_len = (const int64_t*)tab[1];
-  hipLaunchKernelGGL(imp::row_chunk_max_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, d_x, d_off, d_len,
-                     (int64_t)0, d_chunk, chunks);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)B), dim3(imp::kPeakThreads), 0, s, d_x, d_off, d_len,
-                     (int64_t)0, (const unsigned*)nullptr, 0, (const unsigned*)d_chunk, chunks, d_res, peak_height, (long long*)nullptr);
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch_first_peaks(s, d_x, d_off, d_len, B, d_chunk, chunks, d_res, peak_height, nullptr))) return rc;
   std::vector<imp::RowPeak> h((size_t)B);
   HIP_TRY(hipMemcpyAsync(h.data(), d_res, res_bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1797,10 +1852,9 @@ extern "C" int imp_chain_execute_device(imp_chain* c, const float* d_x, int64_t 
     HIP_TRY(hipEventRecord(c->k1_done[(size_t)l], lane_stream));
     HIP_TRY(hipStreamWaitEvent(tail, c->k1_done[(size_t)l], 0));
   }
-  hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)c->B), dim3(imp::kPeakThreads), 0, tail, c->d_ir[(size_t)l],
-                     c->d_meta, c->d_meta + c->B, c->deconv->out_start, (const unsigned*)c->d_tile[(size_t)l], c->tiles,
-                     (const unsigned*)nullptr, c->chunks, c->d_res[(size_t)l], c->peak_height, d_peaks_out);
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch_first_peaks(tail, c->d_ir[(size_t)l], c->d_meta, c->d_meta + c->B, c->B, nullptr, c->chunks, c->d_res[(size_t)l],
+                               c->peak_height, d_peaks_out, c->deconv->out_start, c->d_tile[(size_t)l], c->tiles)))
+    return rc;
   imp::LoadCropAtPeak ld{c->d_ir[(size_t)l], c->pitch_ir, c->deconv->out_len, c->d_res[(size_t)l], c->n, c->head, c->fade_in, c->fade_out,
                          c->d_win};
   bool tail2 = false;
@@ -2023,46 +2077,28 @@ extern "C" int imp_decay_knees_device(imp_ctx* ctx, const float* d_x, const int6
     if (len[b] >= ((int64_t)1 << 31)) return fail(IMP_ERR_INVALID, "row %lld is too long (%lld samples)", (long long)b, (long long)len[b]);
   if ((rc = ctx_bind(ctx))) return rc;
   const int64_t maxlen = sp.maxlen;
-  const int64_t two_fs = (int64_t)(2 * fs);               // int(2 * fs), core/decay.py:84
-  const int64_t span_max = std::max<int64_t>(1, std::min(two_fs, maxlen));
   const int64_t chunks = std::max<int64_t>(1, (maxlen + imp::kPeakChunk - 1) / imp::kPeakChunk);
-  const int mean_pitch = imp::kKneeMaxWindows + 1;
-  // scratch: span maxima bits [B] | peak results [B] | search state [B] | window means [B][mean_pitch] | chunk maxima
+  // scratch: span maxima bits [B] | peak results [B] | search state [B] | window means [B][kKneeMeanPitch] | chunk maxima
   // [B][chunks]; off[B], len[B] through the staging ring.  The spans are read where they are (fp32 rows): no fp64 copy
   // of them is made.
   const size_t meta = (size_t)B * sizeof(int64_t);
   size_t bytes = (size_t)B * sizeof(unsigned long long) + (size_t)B * sizeof(imp::RowPeak) + (size_t)B * sizeof(imp::KneeRow) +
-                 (size_t)B * mean_pitch * sizeof(double) + (size_t)(B * chunks) * sizeof(unsigned);
+                 (size_t)B * kKneeMeanPitch * sizeof(double) + (size_t)(B * chunks) * sizeof(unsigned);
   void* scr = nullptr;
   if ((rc = ctx_scratch(ctx, bytes, &scr))) return rc;
   unsigned long long* d_max = (unsigned long long*)scr;
   imp::RowPeak* d_res = (imp::RowPeak*)(d_max + B);
   imp::KneeRow* d_rows = (imp::KneeRow*)(d_res + B);
   double* d_means = (double*)(d_rows + B);
-  unsigned* d_chunk = (unsigned*)(d_means + (size_t)B * mean_pitch);
+  unsigned* d_chunk = (unsigned*)(d_means + (size_t)B * kKneeMeanPitch);
   hipStream_t s = ctx->stream;
   std::vector<imp::KneeRow> h((size_t)B);
   void* tab[2];
   if ((rc = ctx_stage_tables(ctx, {{off, meta}, {len, meta}}, tab))) return rc;
   const int64_t *d_off = (const int64_t*)tab[0], *d_len = (const int64_t*)tab[1];
-  hipLaunchKernelGGL(imp::row_chunk_max_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, s, d_x, d_off, d_len,
-                     (int64_t)0, d_chunk, chunks);
-  hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)B), dim3(imp::kPeakThreads), 0, s, d_x, d_off, d_len,
-                     (int64_t)0, (const unsigned*)nullptr, 0, (const unsigned*)d_chunk, chunks, d_res, peak_height,
-                     (long long*)nullptr);
-  hipLaunchKernelGGL(imp::knee_span_kernel, dim3((unsigned)B), dim3(64), 0, s, (const imp::RowPeak*)d_res, d_off, d_len,
-                     (long long)two_fs, fs, d_rows, d_max);
-  const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(64, (span_max + 8191) / 8192));
-  dim3 block(256);
-  hipLaunchKernelGGL(imp::knee_maxabs_kernel, dim3((unsigned)bpr, (unsigned)B), block, 0, s, d_x, (const imp::KneeRow*)d_rows, d_max);
-  hipLaunchKernelGGL(imp::knee_windows_kernel, dim3(imp::kKneeRound1, (unsigned)B), block, 0, s, (const imp::KneeRow*)d_rows,
-                     d_x, (const unsigned long long*)d_max, d_means, mean_pitch, 1);
-  hipLaunchKernelGGL(imp::knee_stage1_kernel, dim3((unsigned)B), dim3(64), 0, s, d_rows, (const double*)d_means, mean_pitch, fs);
-  hipLaunchKernelGGL(imp::knee_windows_kernel, dim3(64, (unsigned)B), block, 0, s, (const imp::KneeRow*)d_rows, d_x,
-                     (const unsigned long long*)d_max, d_means, mean_pitch, 0);
-  hipLaunchKernelGGL(imp::knee_stage2_kernel, dim3((unsigned)B), block, 0, s, d_rows, (const double*)d_means, mean_pitch, d_x,
-                     (const unsigned long long*)d_max, fs);
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch_first_peaks(s, d_x, d_off, d_len, B, d_chunk, chunks, d_res, peak_height, nullptr)) ||
+      (rc = launch_knee_search(s, d_x, d_off, d_len, B, maxlen, fs, KneeScratch{d_res, d_max, d_rows, d_means})))
+    return rc;
   HIP_TRY(hipMemcpyAsync(h.data(), d_rows, (size_t)B * sizeof(imp::KneeRow), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   for (int64_t b = 0; b < B; ++b) {
@@ -2390,9 +2426,8 @@ extern "C" int imp_shift_rows_device(imp_ctx* ctx, const float* d_src, const int
   const size_t meta = (size_t)B * sizeof(int64_t);
   void* tab[4];
   if ((rc = ctx_stage_tables(ctx, {{src_off, meta}, {len, meta}, {shift, meta}, {dst_off, meta}}, tab))) return rc;
-  hipLaunchKernelGGL(imp::shift_rows_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (sp.maxlen + 1023) / 1024)), (unsigned)B), dim3(256), 0,
-                     ctx->stream, d_src, (const int64_t*)tab[0], (const int64_t*)tab[1], (const long long*)nullptr, (const long long*)tab[2], d_dst,
-                     (const int64_t*)tab[3]);
+  hipLaunchKernelGGL(imp::shift_rows_kernel, rows_grid(sp.maxlen, B), dim3(256), 0, ctx->stream, d_src, (const int64_t*)tab[0],
+                     (const int64_t*)tab[1], (const long long*)nullptr, (const long long*)tab[2], d_dst, (const int64_t*)tab[3]);
   HIP_TRY(hipGetLastError());
   return IMP_OK;
 }
@@ -2427,10 +2462,8 @@ extern "C" int imp_apply_window(imp_ctx* ctx, float* x, const int64_t* off, cons
   const size_t meta = (size_t)B * sizeof(int64_t);
   void* tab[3];
   if ((rc = ctx_stage_tables(ctx, {{off, meta}, {len, meta}, {params, (size_t)B * sizeof(imp_window_params)}}, tab))) return rc;
-  const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(256, (sp.maxlen + 1023) / 1024));
-  dim3 grid((unsigned)bpr, (unsigned)B), block(256);
-  hipLaunchKernelGGL(imp::apply_window_kernel, grid, block, 0, s, d_x, (const int64_t*)tab[0], (const int64_t*)tab[1],
-                     (const imp::WindowParams*)tab[2]);
+  hipLaunchKernelGGL(imp::apply_window_kernel, rows_grid(sp.maxlen, B), dim3(256), 0, s, d_x, (const int64_t*)tab[0],
+                     (const int64_t*)tab[1], (const imp::WindowParams*)tab[2]);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(x, d_x, (size_t)sp.extent * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -2453,11 +2486,8 @@ extern "C" int imp_apply_window_device(imp_ctx* ctx, const float* d_src, const i
   void* tab[4];
   if ((rc = ctx_stage_tables(ctx, {{src_off, meta}, {dst_off, meta}, {len, meta}, {params, (size_t)B * sizeof(imp_window_params)}}, tab)))
     return rc;
-  const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(256, (sp.maxlen + 1023) / 1024));
-  hipLaunchKernelGGL(imp::apply_window_copy_kernel, dim3((unsigned)bpr, (unsigned)B), dim3(256), 0, ctx->stream, d_src, (const int64_t*)tab[0],
-                     d_dst, (const int64_t*)tab[1], (const int64_t*)tab[2], (const imp::WindowParams*)tab[3]);
-  HIP_TRY(hipGetLastError());
-  return IMP_OK;
+  return launch_window_copy(ctx->stream, d_src, (const int64_t*)tab[0], d_dst, (const int64_t*)tab[1], (const int64_t*)tab[2],
+                            (const imp::WindowParams*)tab[3], sp.maxlen, B);
 }
 
 extern "C" int imp_rows_to_pcm_device(imp_ctx* ctx, const float* d_rows, const int64_t* off, const int64_t* len,

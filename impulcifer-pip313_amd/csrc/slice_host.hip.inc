@@ -82,6 +82,29 @@ struct imp_slice {
   int64_t last_M = 0;
 };
 
+// One block of small device tables, 256-byte aligned each.  A block's tables stand in ONE list of (pointer member, element
+// count): run with no base it only sizes the block (`need`), run with the allocation it points the members into it.
+struct TableCarver {
+  char* base = nullptr;
+  size_t need = 0;
+  template <class T>
+  void operator()(T*& p, size_t count) {
+    if (base) p = (T*)(base + need);
+    need += (count * sizeof(T) + 255) & ~(size_t)255;
+  }
+};
+// sizes the block of `tables` (a callable over a TableCarver&), allocates it into `block` and places the tables
+template <class F>
+static bool carve_tables(char*& block, size_t* need, F&& tables) {
+  TableCarver size, place;
+  tables(size);
+  *need = size.need;
+  if (hipMalloc((void**)&block, size.need) != hipSuccess) return false;
+  place.base = block;
+  tables(place);
+  return true;
+}
+
 static_assert(sizeof(imp::SliceRowOut) == sizeof(imp_slice_row_result), "imp_slice_row_result layout");
 static_assert(sizeof(imp::SliceMeasOut) == sizeof(imp_slice_result), "imp_slice_result layout");
 static_assert(sizeof(imp::WindowParams) == sizeof(imp_window_params), "imp_window_params layout");
@@ -174,52 +197,23 @@ extern "C" int imp_slice_create(imp_plan* deconv, const imp_slice_geometry* g, i
   if ((rc = slice_norm_create(ctx, s->out_len_max, M, &s->norm))) return bail(rc);
   // the small tables as one block
   size_t need = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = need;
-    need += (bytes + 255) & ~(size_t)255;
-    return at;
-  };
-  const size_t o_res = take((size_t)B * sizeof(imp::RowPeak)), o_res2 = take((size_t)B * sizeof(imp::RowPeak));
-  const size_t o_meta = take((size_t)(2 * B) * 8), o_off2 = take((size_t)B * 8), o_len2 = take((size_t)B * 8), o_fl = take((size_t)B * 8);
-  const size_t o_fp = take((size_t)B * sizeof(imp::WindowParams)), o_gp = take((size_t)B * sizeof(imp::WindowParams));
-  const size_t o_delay = take((size_t)s->n_pairs * 8), o_knee = take((size_t)B * sizeof(imp::KneeRow)), o_max = take((size_t)B * 8);
-  const size_t o_go = take((size_t)B * 8), o_gl = take((size_t)B * 8);
-  const size_t o_keep = take((size_t)M * 8), o_ol = take((size_t)M * 8), o_pk = take((size_t)(2 * M) * 8);
-  const size_t o_rows = take((size_t)B * sizeof(imp::SliceRowOut)), o_meas = take((size_t)M * sizeof(imp::SliceMeasOut)),
-               o_flags = take((size_t)M * sizeof(int));
-  const int mean_pitch = imp::kKneeMaxWindows + 1;
-  bool ok = hipMalloc((void**)&s->d_block, need) == hipSuccess &&
+  bool ok = carve_tables(s->d_block, &need, [&](TableCarver& t) {
+              t(s->d_res, B), t(s->d_res2, B), t(s->d_meta, 2 * B), t(s->d_off2, B), t(s->d_len2, B), t(s->d_fade_len, B);
+              t(s->d_fade_par, B), t(s->d_g_par, B), t(s->d_delay, s->n_pairs), t(s->d_knee, B), t(s->d_max, B);
+              t(s->d_g_off, B), t(s->d_g_len, B), t(s->d_keep, M), t(s->d_outlen, M), t(s->d_peak_db, 2 * M);
+              t(s->d_rows, B), t(s->d_meas, M), t(s->d_flags, M);
+            }) &&
             hipMalloc((void**)&s->d_ir, (size_t)(B * s->pitch_ir) * sizeof(float)) == hipSuccess &&
             hipMalloc((void**)&s->d_win, (size_t)std::max<int64_t>(s->fade_out, 1) * sizeof(double)) == hipSuccess &&
             hipMalloc((void**)&s->d_tile, (size_t)std::max<int64_t>(B * s->tiles * s->chunks, 1) * sizeof(unsigned)) == hipSuccess &&
             hipMalloc((void**)&s->d_chunk, (size_t)(B * s->knee_chunks) * sizeof(unsigned)) == hipSuccess &&
-            hipMalloc((void**)&s->d_means, (size_t)B * mean_pitch * sizeof(double)) == hipSuccess &&
+            hipMalloc((void**)&s->d_means, (size_t)B * kKneeMeanPitch * sizeof(double)) == hipSuccess &&
             hipHostMalloc((void**)&s->h_rows, (size_t)B * sizeof(imp::SliceRowOut), hipHostMallocDefault) == hipSuccess &&
             hipHostMalloc((void**)&s->h_meas, (size_t)M * sizeof(imp::SliceMeasOut), hipHostMallocDefault) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     return bail(fail(IMP_ERR_ALLOC, "imp_slice_create: device allocation for %lld measurements of %lld rows failed", (long long)M, (long long)s->R));
   }
-  char* blk = s->d_block;
-  s->d_res = (imp::RowPeak*)(blk + o_res);
-  s->d_res2 = (imp::RowPeak*)(blk + o_res2);
-  s->d_meta = (int64_t*)(blk + o_meta);
-  s->d_off2 = (int64_t*)(blk + o_off2);
-  s->d_len2 = (int64_t*)(blk + o_len2);
-  s->d_fade_len = (int64_t*)(blk + o_fl);
-  s->d_fade_par = (imp::WindowParams*)(blk + o_fp);
-  s->d_g_par = (imp::WindowParams*)(blk + o_gp);
-  s->d_delay = (long long*)(blk + o_delay);
-  s->d_knee = (imp::KneeRow*)(blk + o_knee);
-  s->d_max = (unsigned long long*)(blk + o_max);
-  s->d_g_off = (int64_t*)(blk + o_go);
-  s->d_g_len = (int64_t*)(blk + o_gl);
-  s->d_keep = (long long*)(blk + o_keep);
-  s->d_outlen = (long long*)(blk + o_ol);
-  s->d_peak_db = (double*)(blk + o_pk);
-  s->d_rows = (imp::SliceRowOut*)(blk + o_rows);
-  s->d_meas = (imp::SliceMeasOut*)(blk + o_meas);
-  s->d_flags = (int*)(blk + o_flags);
   std::vector<int64_t> meta((size_t)(2 * B));
   for (int64_t b = 0; b < B; ++b) {
     meta[(size_t)b] = b * s->pitch_ir;
@@ -296,21 +290,14 @@ extern "C" int imp_slice_set_alignment(imp_slice* s, int64_t n_ipsi, const int32
     if (leader_of_pair[q] >= s->n_pairs) return fail(IMP_ERR_INVALID, "imp_slice_set_alignment: leader of pair %lld out of range", (long long)q);
   if (!s->d_ablock) {
     const int64_t J = s->m_cap * s->n_pairs;                  // jobs: at most one per pair and measurement
-    size_t need = 0;
-    auto take = [&](size_t bytes) {
-      const size_t at = need;
-      need += (bytes + 255) & ~(size_t)255;
-      return at;
-    };
-    const size_t o_ia = take((size_t)s->n_pairs * 4), o_ib = take((size_t)s->n_pairs * 4), o_ld = take((size_t)s->n_pairs * 4);
-    const size_t o_lds = take((size_t)s->n_pairs * 4);
-    const size_t o_ao = take((size_t)J * 8), o_al = take((size_t)J * 8), o_bo = take((size_t)J * 8), o_bl = take((size_t)J * 8);
-    const size_t o_arg = take((size_t)J * 8), o_val = take((size_t)J * 8);
     const int64_t S_max = xcorr_slices(16384);
-    const size_t o_pk = take((size_t)(J * S_max) * 8), o_pv = take((size_t)(J * S_max) * 8);
-    const size_t o_l1 = take((size_t)B * 8), o_d1 = take((size_t)B * 8), o_s2 = take((size_t)B * 8), o_r1 = take((size_t)B * sizeof(imp::RowPeak));
-    const size_t o_oa = take((size_t)B * 8);
-    bool ok = hipMalloc((void**)&s->d_ablock, need) == hipSuccess &&
+    size_t need = 0;
+    bool ok = carve_tables(s->d_ablock, &need, [&](TableCarver& t) {
+                t(s->d_ipsi_a, s->n_pairs), t(s->d_ipsi_b, s->n_pairs), t(s->d_leader, s->n_pairs), t(s->d_leads, s->n_pairs);
+                t(s->d_xa_off, J), t(s->d_xa_len, J), t(s->d_xb_off, J), t(s->d_xb_len, J), t(s->d_xarg, J), t(s->d_xval, J);
+                t(s->d_xpart_k, J * S_max), t(s->d_xpart_val, J * S_max);
+                t(s->d_len1, B), t(s->d_d1, B), t(s->d_s2, B), t(s->d_res1, B), t(s->d_off_al, B);
+              }) &&
               hipMalloc((void**)&s->d_ir2, (size_t)(B * s->pitch_ir) * sizeof(float)) == hipSuccess;
     if (!ok) {
       (void)hipGetLastError();
@@ -320,24 +307,6 @@ extern "C" int imp_slice_set_alignment(imp_slice* s, int64_t n_ipsi, const int32
       s->d_ir2 = nullptr;
       return fail(IMP_ERR_ALLOC, "imp_slice_set_alignment: device allocation for %lld rows of %lld samples failed", (long long)B, (long long)s->pitch_ir);
     }
-    char* blk = s->d_ablock;
-    s->d_ipsi_a = (int*)(blk + o_ia);
-    s->d_ipsi_b = (int*)(blk + o_ib);
-    s->d_leader = (int*)(blk + o_ld);
-    s->d_leads = (int*)(blk + o_lds);
-    s->d_xa_off = (int64_t*)(blk + o_ao);
-    s->d_xa_len = (int64_t*)(blk + o_al);
-    s->d_xb_off = (int64_t*)(blk + o_bo);
-    s->d_xb_len = (int64_t*)(blk + o_bl);
-    s->d_xarg = (long long*)(blk + o_arg);
-    s->d_xval = (double*)(blk + o_val);
-    s->d_xpart_k = (long long*)(blk + o_pk);
-    s->d_xpart_val = (double*)(blk + o_pv);
-    s->d_len1 = (int64_t*)(blk + o_l1);
-    s->d_d1 = (long long*)(blk + o_d1);
-    s->d_s2 = (long long*)(blk + o_s2);
-    s->d_res1 = (imp::RowPeak*)(blk + o_r1);
-    s->d_off_al = (int64_t*)(blk + o_oa);
     HIP_TRY(hipMemsetAsync(s->d_ablock, 0, need, ctx->stream));
   }
   if (n_ipsi) {
@@ -382,14 +351,10 @@ extern "C" int imp_slice_set_decay(imp_slice* s, const double* target_rt60) {
     s->dchunks = std::max<int64_t>(1, (s->out_len_max + imp::kPeakChunk - 1) / imp::kPeakChunk);
     s->dscratch = 2 * (s->out_len_max + 2);
     size_t need = 0;
-    auto take = [&](size_t bytes) {
-      const size_t at = need;
-      need += (bytes + 255) & ~(size_t)255;
-      return at;
-    };
-    const size_t o_off = take((size_t)B * 8), o_len = take((size_t)B * 8), o_dl = take((size_t)B * 8), o_res = take((size_t)B * sizeof(imp::RowPeak));
-    const size_t o_jobs = take((size_t)B * sizeof(imp::DecayJob)), o_rt = take((size_t)(4 * B) * 8), o_par = take((size_t)B * sizeof(imp::WindowParams));
-    bool ok = hipMalloc((void**)&s->d_target, (size_t)s->R * 8) == hipSuccess && hipMalloc((void**)&s->d_dblock, need) == hipSuccess &&
+    bool ok = hipMalloc((void**)&s->d_target, (size_t)s->R * 8) == hipSuccess &&
+              carve_tables(s->d_dblock, &need, [&](TableCarver& t) {
+                t(s->d_off3, B), t(s->d_len3, B), t(s->d_dlen, B), t(s->d_res3, B), t(s->d_jobs, B), t(s->d_rt, 4 * B), t(s->d_dpar, B);
+              }) &&
               hipMalloc((void**)&s->d_dchunk, (size_t)(B * s->dchunks) * sizeof(unsigned)) == hipSuccess &&
               hipMalloc((void**)&s->d_dscr, (size_t)(B * s->dscratch) * sizeof(double)) == hipSuccess;
     if (!ok) {
@@ -404,14 +369,6 @@ extern "C" int imp_slice_set_decay(imp_slice* s, const double* target_rt60) {
       s->d_dscr = nullptr;
       return fail(IMP_ERR_ALLOC, "imp_slice_set_decay: device allocation for %lld rows of %lld samples failed", (long long)B, (long long)s->out_len_max);
     }
-    char* blk = s->d_dblock;
-    s->d_off3 = (int64_t*)(blk + o_off);
-    s->d_len3 = (int64_t*)(blk + o_len);
-    s->d_dlen = (int64_t*)(blk + o_dl);
-    s->d_res3 = (imp::RowPeak*)(blk + o_res);
-    s->d_jobs = (imp::DecayJob*)(blk + o_jobs);
-    s->d_rt = (double*)(blk + o_rt);
-    s->d_dpar = (imp::WindowParams*)(blk + o_par);
     HIP_TRY(hipMemsetAsync(s->d_dblock, 0, need, ctx->stream));
   }
   HIP_TRY(hipMemcpyAsync(s->d_target, target_rt60, (size_t)s->R * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -455,40 +412,17 @@ extern "C" int imp_slice_set_virtual_bass(imp_slice* s, const double* sos_hp, in
     s->vb_spans = (s->keep_cap + imp::kVbRefSpan - 1) / imp::kVbRefSpan;
     const int64_t M = s->m_cap, C = s->vb_chunks;
     size_t need = 0;
-    auto take = [&](size_t bytes) {
-      const size_t at = need;
-      need += (bytes + 255) & ~(size_t)255;
-      return at;
-    };
-    const size_t o_vb = take((size_t)(B * s->pitch_crop) * 4), o_end = take((size_t)(B * C) * imp::kIirState * 8),
-                 o_init = take((size_t)(B * C) * imp::kIirState * 8), o_part = take((size_t)(B * C) * 16),
-                 o_refp = take((size_t)(M * s->vb_spans) * 16), o_mp = take((size_t)s->keep_cap * 8), o_ild = take((size_t)s->keep_cap * 8),
-                 o_P = take(256 * 8), o_gp = take((size_t)M * 8), o_left = take((size_t)s->n_pairs * 4), o_off = take((size_t)B * 8),
-                 o_len = take((size_t)B * 8), o_par = take((size_t)B * sizeof(imp::WindowParams)), o_bin = take((size_t)M * 8),
-                 o_rows = take((size_t)B * sizeof(imp::VbRow)), o_res = take((size_t)B * sizeof(imp::RowPeak));
-    if (hipMalloc((void**)&s->d_vbblock, need) != hipSuccess) {
+    if (!carve_tables(s->d_vbblock, &need, [&](TableCarver& t) {
+          t(s->d_vb, B * s->pitch_crop), t(s->d_vb_end, B * C * imp::kIirState), t(s->d_vb_init, B * C * imp::kIirState);
+          t(s->d_vb_part, B * C * 2), t(s->d_vb_refp, M * s->vb_spans * 2), t(s->d_vb_mp, s->keep_cap), t(s->d_vb_ild, s->keep_cap);
+          t(s->d_vb_P, 256), t(s->d_vb_gp, M), t(s->d_vb_left, s->n_pairs), t(s->d_vb_off, B), t(s->d_vb_len, B), t(s->d_vb_par, B);
+          t(s->d_vb_bin, M), t(s->d_vb_rows, B), t(s->d_vb_res, B);
+        })) {
       (void)hipGetLastError();
       s->d_vbblock = nullptr;
       return fail(IMP_ERR_ALLOC, "imp_slice_set_virtual_bass: device allocation for %lld rows of %lld samples failed", (long long)B,
                   (long long)s->pitch_crop);
     }
-    char* blk = s->d_vbblock;
-    s->d_vb = (float*)(blk + o_vb);
-    s->d_vb_end = (double*)(blk + o_end);
-    s->d_vb_init = (double*)(blk + o_init);
-    s->d_vb_part = (double*)(blk + o_part);
-    s->d_vb_refp = (double*)(blk + o_refp);
-    s->d_vb_mp = (double*)(blk + o_mp);
-    s->d_vb_ild = (double*)(blk + o_ild);
-    s->d_vb_P = (double*)(blk + o_P);
-    s->d_vb_gp = (double*)(blk + o_gp);
-    s->d_vb_left = (int*)(blk + o_left);
-    s->d_vb_off = (int64_t*)(blk + o_off);
-    s->d_vb_len = (int64_t*)(blk + o_len);
-    s->d_vb_par = (imp::WindowParams*)(blk + o_par);
-    s->d_vb_bin = (long long*)(blk + o_bin);
-    s->d_vb_rows = (imp::VbRow*)(blk + o_rows);
-    s->d_vb_res = (imp::RowPeak*)(blk + o_res);
     HIP_TRY(hipMemsetAsync(s->d_vbblock, 0, need, ctx->stream));
   }
   std::vector<double> P(256);
@@ -524,15 +458,10 @@ static int slice_vbass_run(imp_slice* s, hipStream_t st, int64_t M, const float*
   const int64_t R = s->R, B = M * R, C = s->vb_chunks;
   hipLaunchKernelGGL(imp::vbass_tables_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, (const long long*)s->d_keep, (int)R, (int)B,
                      (long long)s->pitch_crop, (long long)s->fade_out, s->fs, s->vb_xo, s->d_vb_off, s->d_vb_len, s->d_vb_par, s->d_vb_bin);
-  hipLaunchKernelGGL(imp::apply_window_copy_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (s->keep_cap + 1023) / 1024)), (unsigned)B),
-                     dim3(256), 0, st, rows_al, off_al, s->d_vb, (const int64_t*)s->d_vb_off, (const int64_t*)s->d_vb_len,
-                     (const imp::WindowParams*)s->d_vb_par);
-  hipLaunchKernelGGL(imp::row_chunk_max_kernel, dim3((unsigned)s->knee_chunks, (unsigned)B), dim3(256), 0, st, (const float*)s->d_vb,
-                     (const int64_t*)s->d_vb_off, (const int64_t*)s->d_vb_len, (int64_t)0, s->d_chunk, s->knee_chunks);
-  hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)B), dim3(imp::kPeakThreads), 0, st, (const float*)s->d_vb,
-                     (const int64_t*)s->d_vb_off, (const int64_t*)s->d_vb_len, (int64_t)0, (const unsigned*)nullptr, 0, (const unsigned*)s->d_chunk,
-                     s->knee_chunks, s->d_vb_res, s->peak_height, (long long*)nullptr);
-  HIP_TRY(hipGetLastError());
+  int rc;
+  if ((rc = launch_window_copy(st, rows_al, off_al, s->d_vb, s->d_vb_off, s->d_vb_len, s->d_vb_par, s->keep_cap, B)) ||
+      (rc = launch_first_peaks(st, s->d_vb, s->d_vb_off, s->d_vb_len, B, s->d_chunk, s->knee_chunks, s->d_vb_res, s->peak_height, nullptr)))
+    return rc;
   const dim3 grid((unsigned)((C + 63) / 64), (unsigned)B);
   hipLaunchKernelGGL(imp::iir_chunk_end_kernel<float>, grid, dim3(64), 0, st, s->vb_sos, (const float*)s->d_vb, (const int64_t*)s->d_vb_off,
                      (const int64_t*)s->d_vb_len, s->d_vb_end, (long long)C);
@@ -589,6 +518,120 @@ static int slice_ingest_typed(imp_slice* s, const Sample* rec, int64_t m, float 
   return rc;
 }
 
+// ---- the stages of imp_slice_execute_device, in the order of core/pipeline.py; B = M R rows throughout
+// K1: every column of every measurement -> d_ir (pair mode: pass C also leaves the chunk maxima)
+static int slice_ingest(imp_slice* s, const void* d_rec, int64_t rec_stride, int64_t M) {
+  for (int64_t m = 0; m < M; ++m) {
+    const int rc = s->bits == 32 ? slice_ingest_typed<int>(s, (const int*)d_rec + m * rec_stride, m, 1.0f / 2147483648.0f)
+                                 : slice_ingest_typed<short>(s, (const short*)d_rec + m * rec_stride, m, 1.0f / 32768.0f);
+    if (rc) return rc;
+  }
+  return IMP_OK;
+}
+
+// K3: first peaks of the deconvolved columns
+static int slice_first_peaks(imp_slice* s, hipStream_t st, int64_t M) {
+  const int64_t* len = s->d_meta + s->m_cap * s->R;
+  if (s->deconv->paired)
+    return launch_first_peaks(st, s->d_ir, s->d_meta, len, M * s->R, nullptr, s->chunks, s->d_res, s->peak_height, nullptr,
+                              s->deconv->out_start, s->d_tile, s->tiles);
+  return launch_first_peaks(st, s->d_ir, s->d_meta, len, M * s->R, s->d_chunk, s->knee_chunks, s->d_res, s->peak_height, nullptr);
+}
+
+// crop_heads: offsets and lengths on the device, Hann fade-in in place
+static int slice_crop_heads(imp_slice* s, hipStream_t st, int64_t M) {
+  const int n_pairs_total = (int)(M * s->n_pairs);
+  hipLaunchKernelGGL(imp::slice_crop_heads_kernel, dim3((unsigned)((n_pairs_total + 63) / 64)), dim3(64), 0, st, (const imp::RowPeak*)s->d_res,
+                     (const long long*)s->d_delay, (int)s->n_pairs, n_pairs_total, (long long)s->pitch_ir, (long long)s->row_len,
+                     (long long)s->head, s->d_off2, s->d_len2, s->d_fade_len, s->d_fade_par, s->d_rows, s->d_flags);
+  if (s->head > 0) return launch_window_copy(st, s->d_ir, s->d_off2, s->d_ir, s->d_off2, s->d_fade_len, s->d_fade_par, s->head, M * s->R);
+  HIP_TRY(hipGetLastError());
+  return IMP_OK;
+}
+
+// alignment (core/pipeline.py:593-597): ipsilateral lags (K10), onset shifts from the leaders' peaks, the rows materialised.
+// The later stages read row b at d_ir + d_off_al[b]: crop_heads' place, or the copy in d_ir2.
+static int slice_align(imp_slice* s, hipStream_t st, int64_t M) {
+  const int64_t R = s->R, B = M * R;
+  const int n_jobs = (int)(M * s->n_ipsi);
+  int rc;
+  HIP_TRY(hipMemsetAsync(s->d_xarg, 0, (size_t)std::max(n_jobs, 1) * 8, st));
+  if (n_jobs) {
+    hipLaunchKernelGGL(imp::slice_align_jobs_kernel, dim3((unsigned)((n_jobs + 63) / 64)), dim3(64), 0, st, (const int64_t*)s->d_off2,
+                       (const int64_t*)s->d_len2, (const int*)s->d_ipsi_a, (const int*)s->d_ipsi_b, s->n_ipsi, (int)R, n_jobs, (long long)s->segment,
+                       s->d_xa_off, s->d_xa_len, s->d_xb_off, s->d_xb_len, s->d_flags);
+    if ((rc = launch_xcorr<float>(s->ctx, st, (const float*)s->d_ir, (const int64_t*)s->d_xa_off, (const int64_t*)s->d_xa_len, (const float*)s->d_ir,
+                                  (const int64_t*)s->d_xb_off, (const int64_t*)s->d_xb_len, n_jobs, imp::xcorr_lds_doubles(s->segment, s->segment), 2 * s->segment - 1,
+                                  s->d_xpart_k, s->d_xpart_val, s->d_xarg, s->d_xval)))
+      return rc;
+  }
+  hipLaunchKernelGGL(imp::slice_align_delays_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, st, (const long long*)s->d_xarg,
+                     (const int64_t*)s->d_xa_len, (const int*)s->d_ipsi_a, (const int*)s->d_ipsi_b, s->n_ipsi, (int)R, (int)M,
+                     (const int64_t*)s->d_len2, (const int*)s->d_leads, s->d_d1, s->d_len1);
+  if ((rc = launch_first_peaks(st, s->d_ir, s->d_off2, s->d_len1, B, s->d_chunk, s->knee_chunks, s->d_res1, s->peak_height, nullptr))) return rc;
+  hipLaunchKernelGGL(imp::slice_align_onset_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, st, (const imp::RowPeak*)s->d_res1,
+                     (const long long*)s->d_d1, (const int64_t*)s->d_len1, (const float*)s->d_ir, (const int64_t*)s->d_off2,
+                     (const int*)s->d_leader, s->ref_pair, (int)R, (int)M, s->d_s2, (long long)(s->d_ir2 - s->d_ir), (long long)s->pitch_ir,
+                     s->d_off_al, s->d_rows, s->d_flags);
+  hipLaunchKernelGGL(imp::shift_rows_kernel, rows_grid(s->row_len, B), dim3(256), 0, st, (const float*)s->d_ir, (const int64_t*)s->d_off2,
+                     (const int64_t*)s->d_len2, (const long long*)s->d_d1, (const long long*)s->d_s2, s->d_ir2, (const int64_t*)s->d_meta);
+  HIP_TRY(hipGetLastError());
+  return IMP_OK;
+}
+
+// crop_tails: peak + Lundeby knee search of the cropped rows (K7c), the common length (truncation + fade-out: K5's loader)
+static int slice_crop_tails(imp_slice* s, hipStream_t st, int64_t M, const int64_t* off_al) {
+  const int64_t B = M * s->R;
+  int rc;
+  if ((rc = launch_first_peaks(st, s->d_ir, off_al, s->d_len2, B, s->d_chunk, s->knee_chunks, s->d_res2, s->peak_height, nullptr)) ||
+      (rc = launch_knee_search(st, s->d_ir, off_al, s->d_len2, B, s->row_len, s->fs, KneeScratch{s->d_res2, s->d_max, s->d_knee, s->d_means})))
+    return rc;
+  hipLaunchKernelGGL(imp::slice_keep_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, st, (const imp::KneeRow*)s->d_knee,
+                     off_al, (const int64_t*)s->d_len2, (int)s->R, (int)M, (long long)s->fade_out, (long long)s->keep_cap,
+                     (long long)s->taps, s->d_keep, s->d_outlen, s->d_rows, s->d_meas, s->d_flags);
+  HIP_TRY(hipGetLastError());
+  return IMP_OK;
+}
+
+// equalize: K5 over every row, straight from the rows it is given - offsets, lengths and the fade-out from the device
+static int slice_equalize(imp_slice* s, hipStream_t st, int64_t M, const float* rows, const int64_t* off, long long fade_out, float* d_out,
+                          int64_t out_pitch) {
+  imp_plan* f = s->fir;
+  f->cur_stream = st;
+  imp::LoadRowsDeviceLen ld{rows, off, (const long long*)s->d_keep, (int)s->R, (long long)s->taps, fade_out, (const double*)s->d_win};
+  return launch_fir_block(f, ld, M * s->R, d_out, out_pitch, 0);
+}
+
+// adjust decay: decay_params (K3 + K7c) + decay_times of the equalized rows that have a target, the window in place
+static int slice_decay(imp_slice* s, hipStream_t st, int64_t M, float* d_out, int64_t out_pitch) {
+  const int64_t R = s->R, B = M * R;
+  int rc;
+  hipLaunchKernelGGL(imp::slice_decay_rows_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, (const long long*)s->d_outlen, (int)R, (int)B,
+                     (long long)out_pitch, s->d_off3, s->d_len3);
+  if ((rc = launch_first_peaks(st, d_out, s->d_off3, s->d_len3, B, s->d_dchunk, s->dchunks, s->d_res3, s->peak_height, nullptr)) ||
+      (rc = launch_knee_search(st, d_out, s->d_off3, s->d_len3, B, s->out_len_max, s->fs, KneeScratch{s->d_res3, s->d_max, s->d_knee, s->d_means})))
+    return rc;
+  hipLaunchKernelGGL(imp::slice_decay_jobs_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, (const imp::KneeRow*)s->d_knee,
+                     (const double*)s->d_target, (int)R, (int)B, (long long)s->dscratch, s->d_jobs);
+  hipLaunchKernelGGL(imp::decay_times_kernel<float>, dim3((unsigned)B), dim3(imp::kDecayThreads), 0, st, (const float*)d_out, (const imp::DecayJob*)s->d_jobs, s->d_dscr,
+                     s->fs, s->d_rt);
+  hipLaunchKernelGGL(imp::slice_decay_params_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, st, (const imp::KneeRow*)s->d_knee,
+                     (const double*)s->d_rt, (const double*)s->d_target, (const int64_t*)s->d_len3, (int)R, (int)M, s->fs, s->d_dlen, s->d_dpar,
+                     s->d_rows, s->d_flags);
+  return launch_window_copy(st, d_out, s->d_off3, d_out, s->d_off3, s->d_dlen, s->d_dpar, s->out_len_max, B);
+}
+
+// normalize: maxima of the ear sums' spectra, gain on the device, applied in place
+static int slice_normalize(imp_slice* s, hipStream_t st, int64_t M, float* d_out, int64_t out_pitch) {
+  const int64_t R = s->R;
+  int rc;
+  if ((rc = slice_norm_run(s->ctx, s->norm, d_out, out_pitch, (int)R, (const long long*)s->d_outlen, M, s->d_peak_db))) return rc;
+  hipLaunchKernelGGL(imp::slice_gain_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, st, (const double*)s->d_peak_db,
+                     (const long long*)s->d_outlen, (int)R, (int)M, s->peak_target, s->guard_rel, (long long)out_pitch, s->d_g_off, s->d_g_len,
+                     s->d_g_par, s->d_meas, s->d_flags);
+  return launch_window_copy(st, d_out, s->d_g_off, d_out, s->d_g_off, s->d_g_len, s->d_g_par, s->out_len_max, M * R);
+}
+
 extern "C" int imp_slice_execute_device(imp_slice* s, const void* d_rec, int64_t rec_stride, int64_t M, float* d_out,
                                         int64_t out_pitch) {
   if (!s || !d_rec || !d_out) return fail(IMP_ERR_INVALID, "imp_slice_execute_device: null argument");
@@ -603,160 +646,20 @@ extern "C" int imp_slice_execute_device(imp_slice* s, const void* d_rec, int64_t
   int rc = ctx_bind(ctx);
   if (rc) return rc;
   hipStream_t st = ctx->stream;
-  const int64_t R = s->R, B = M * R;
   HIP_TRY(hipMemsetAsync(s->d_flags, 0, (size_t)M * sizeof(int), st));
-  // ---- K1: every column of every measurement -> d_ir (pair mode: pass C also leaves the chunk maxima)
-  for (int64_t m = 0; m < M; ++m) {
-    if (s->bits == 32) rc = slice_ingest_typed<int>(s, (const int*)d_rec + m * rec_stride, m, 1.0f / 2147483648.0f);
-    else rc = slice_ingest_typed<short>(s, (const short*)d_rec + m * rec_stride, m, 1.0f / 32768.0f);
-    if (rc) return rc;
+  if ((rc = slice_ingest(s, d_rec, rec_stride, M)) || (rc = slice_first_peaks(s, st, M)) || (rc = slice_crop_heads(s, st, M))) return rc;
+  if (s->align_on && (rc = slice_align(s, st, M))) return rc;
+  const int64_t* off_al = s->align_on ? s->d_off_al : s->d_off2;
+  if ((rc = slice_crop_tails(s, st, M, off_al))) return rc;
+  if (s->vb_on) {                                          // its rows are truncated and faded already: K5 reads them as they are
+    if ((rc = slice_vbass_run(s, st, M, s->d_ir, off_al)) || (rc = slice_equalize(s, st, M, s->d_vb, s->d_vb_off, 0, d_out, out_pitch))) return rc;
+  } else if ((rc = slice_equalize(s, st, M, s->d_ir, off_al, s->fade_out, d_out, out_pitch))) {
+    return rc;
   }
-  // ---- K3: first peaks of the deconvolved columns
-  if (s->deconv->paired) {
-    hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)B), dim3(imp::kPeakThreads), 0, st, s->d_ir, s->d_meta,
-                       s->d_meta + s->m_cap * R, s->deconv->out_start, (const unsigned*)s->d_tile, s->tiles, (const unsigned*)nullptr,
-                       s->chunks, s->d_res, s->peak_height, (long long*)nullptr);
-  } else {
-    hipLaunchKernelGGL(imp::row_chunk_max_kernel, dim3((unsigned)s->knee_chunks, (unsigned)B), dim3(256), 0, st, s->d_ir, s->d_meta,
-                       s->d_meta + s->m_cap * R, (int64_t)0, s->d_chunk, s->knee_chunks);
-    hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)B), dim3(imp::kPeakThreads), 0, st, s->d_ir, s->d_meta,
-                       s->d_meta + s->m_cap * R, (int64_t)0, (const unsigned*)nullptr, 0, (const unsigned*)s->d_chunk, s->knee_chunks,
-                       s->d_res, s->peak_height, (long long*)nullptr);
-  }
-  HIP_TRY(hipGetLastError());
-  // ---- crop_heads: offsets and lengths on the device, Hann fade-in in place
-  const int n_pairs_total = (int)(M * s->n_pairs);
-  hipLaunchKernelGGL(imp::slice_crop_heads_kernel, dim3((unsigned)((n_pairs_total + 63) / 64)), dim3(64), 0, st, (const imp::RowPeak*)s->d_res,
-                     (const long long*)s->d_delay, (int)s->n_pairs, n_pairs_total, (long long)s->pitch_ir, (long long)s->row_len,
-                     (long long)s->head, s->d_off2, s->d_len2, s->d_fade_len, s->d_fade_par, s->d_rows, s->d_flags);
-  if (s->head > 0)
-    hipLaunchKernelGGL(imp::apply_window_copy_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (s->head + 1023) / 1024)), (unsigned)B),
-                       dim3(256), 0, st, (const float*)s->d_ir, (const int64_t*)s->d_off2, s->d_ir, (const int64_t*)s->d_off2,
-                       (const int64_t*)s->d_fade_len, (const imp::WindowParams*)s->d_fade_par);
-  HIP_TRY(hipGetLastError());
-  // ---- alignment (core/pipeline.py:593-597): ipsilateral lags (K10), onset shifts from the leaders' peaks, the rows materialised
-  const float* rows_al = s->d_ir;
-  const int64_t* off_al = s->d_off2;
-  if (s->align_on) {
-    const int n_jobs = (int)(M * s->n_ipsi);
-    HIP_TRY(hipMemsetAsync(s->d_xarg, 0, (size_t)std::max(n_jobs, 1) * 8, st));
-    if (n_jobs) {
-      hipLaunchKernelGGL(imp::slice_align_jobs_kernel, dim3((unsigned)((n_jobs + 63) / 64)), dim3(64), 0, st, (const int64_t*)s->d_off2,
-                         (const int64_t*)s->d_len2, (const int*)s->d_ipsi_a, (const int*)s->d_ipsi_b, s->n_ipsi, (int)R, n_jobs, (long long)s->segment,
-                         s->d_xa_off, s->d_xa_len, s->d_xb_off, s->d_xb_len, s->d_flags);
-      if ((rc = launch_xcorr<float>(ctx, st, (const float*)s->d_ir, (const int64_t*)s->d_xa_off, (const int64_t*)s->d_xa_len, (const float*)s->d_ir,
-                                    (const int64_t*)s->d_xb_off, (const int64_t*)s->d_xb_len, n_jobs, imp::xcorr_lds_doubles(s->segment, s->segment), 2 * s->segment - 1,
-                                    s->d_xpart_k, s->d_xpart_val, s->d_xarg, s->d_xval)))
-        return rc;
-    }
-    hipLaunchKernelGGL(imp::slice_align_delays_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, st, (const long long*)s->d_xarg,
-                       (const int64_t*)s->d_xa_len, (const int*)s->d_ipsi_a, (const int*)s->d_ipsi_b, s->n_ipsi, (int)R, (int)M,
-                       (const int64_t*)s->d_len2, (const int*)s->d_leads, s->d_d1, s->d_len1);
-    hipLaunchKernelGGL(imp::row_chunk_max_kernel, dim3((unsigned)s->knee_chunks, (unsigned)B), dim3(256), 0, st, s->d_ir, s->d_off2, s->d_len1,
-                       (int64_t)0, s->d_chunk, s->knee_chunks);
-    hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)B), dim3(imp::kPeakThreads), 0, st, s->d_ir, s->d_off2, s->d_len1,
-                       (int64_t)0, (const unsigned*)nullptr, 0, (const unsigned*)s->d_chunk, s->knee_chunks, s->d_res1, s->peak_height,
-                       (long long*)nullptr);
-    hipLaunchKernelGGL(imp::slice_align_onset_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, st, (const imp::RowPeak*)s->d_res1,
-                       (const long long*)s->d_d1, (const int64_t*)s->d_len1, (const float*)s->d_ir, (const int64_t*)s->d_off2,
-                       (const int*)s->d_leader, s->ref_pair, (int)R, (int)M, s->d_s2, (long long)(s->d_ir2 - s->d_ir), (long long)s->pitch_ir,
-                       s->d_off_al, s->d_rows, s->d_flags);
-    hipLaunchKernelGGL(imp::shift_rows_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (s->row_len + 1023) / 1024)), (unsigned)B),
-                       dim3(256), 0, st, (const float*)s->d_ir, (const int64_t*)s->d_off2, (const int64_t*)s->d_len2, (const long long*)s->d_d1,
-                       (const long long*)s->d_s2, s->d_ir2, (const int64_t*)s->d_meta);
-    HIP_TRY(hipGetLastError());
-    off_al = s->d_off_al;                                  // offsets from d_ir: crop_heads' place, or the copy in d_ir2
-  }
-  // ---- crop_tails: peak + Lundeby knee search of the cropped rows (K7c), the common length (truncation + fade-out: K5's loader)
-  {
-    const int64_t two_fs = (int64_t)(2 * s->fs);
-    const int64_t span_max = std::max<int64_t>(1, std::min(two_fs, s->row_len));
-    const int mean_pitch = imp::kKneeMaxWindows + 1;
-    hipLaunchKernelGGL(imp::row_chunk_max_kernel, dim3((unsigned)s->knee_chunks, (unsigned)B), dim3(256), 0, st, rows_al, off_al, s->d_len2,
-                       (int64_t)0, s->d_chunk, s->knee_chunks);
-    hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)B), dim3(imp::kPeakThreads), 0, st, rows_al, off_al, s->d_len2,
-                       (int64_t)0, (const unsigned*)nullptr, 0, (const unsigned*)s->d_chunk, s->knee_chunks, s->d_res2, s->peak_height,
-                       (long long*)nullptr);
-    hipLaunchKernelGGL(imp::knee_span_kernel, dim3((unsigned)B), dim3(64), 0, st, (const imp::RowPeak*)s->d_res2, off_al, s->d_len2,
-                       (long long)two_fs, s->fs, s->d_knee, s->d_max);
-    const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(64, (span_max + 8191) / 8192));
-    hipLaunchKernelGGL(imp::knee_maxabs_kernel, dim3((unsigned)bpr, (unsigned)B), dim3(256), 0, st, rows_al, (const imp::KneeRow*)s->d_knee, s->d_max);
-    hipLaunchKernelGGL(imp::knee_windows_kernel, dim3(imp::kKneeRound1, (unsigned)B), dim3(256), 0, st, (const imp::KneeRow*)s->d_knee, rows_al,
-                       (const unsigned long long*)s->d_max, s->d_means, mean_pitch, 1);
-    hipLaunchKernelGGL(imp::knee_stage1_kernel, dim3((unsigned)B), dim3(64), 0, st, s->d_knee, (const double*)s->d_means, mean_pitch, s->fs);
-    hipLaunchKernelGGL(imp::knee_windows_kernel, dim3(64, (unsigned)B), dim3(256), 0, st, (const imp::KneeRow*)s->d_knee, rows_al,
-                       (const unsigned long long*)s->d_max, s->d_means, mean_pitch, 0);
-    hipLaunchKernelGGL(imp::knee_stage2_kernel, dim3((unsigned)B), dim3(256), 0, st, s->d_knee, (const double*)s->d_means, mean_pitch, rows_al,
-                       (const unsigned long long*)s->d_max, s->fs);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(imp::slice_keep_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, st, (const imp::KneeRow*)s->d_knee,
-                     off_al, (const int64_t*)s->d_len2, (int)R, (int)M, (long long)s->fade_out, (long long)s->keep_cap,
-                     (long long)s->taps, s->d_keep, s->d_outlen, s->d_rows, s->d_meas, s->d_flags);
-  HIP_TRY(hipGetLastError());
-  // ---- virtual bass (core/pipeline.py:603-616): the cropped rows high-passed at the crossover plus the synthesised bass
-  const float* rows_eq = rows_al;
-  const int64_t* off_eq = off_al;
-  long long fade_eq = s->fade_out;
-  if (s->vb_on) {
-    if ((rc = slice_vbass_run(s, st, M, rows_al, off_al))) return rc;
-    rows_eq = s->d_vb;                                     // truncated and faded already: K5 reads them as they are
-    off_eq = s->d_vb_off;
-    fade_eq = 0;
-  }
-  // ---- equalize: K5 over every row, straight from the deconvolved columns - offsets, lengths and the fade-out from the device
-  {
-    imp_plan* f = s->fir;
-    f->cur_stream = st;
-    imp::LoadRowsDeviceLen ld{rows_eq, off_eq, (const long long*)s->d_keep, (int)R, (long long)s->taps,
-                              fade_eq, (const double*)s->d_win};
-    if ((rc = launch_fir_block(f, ld, B, d_out, out_pitch, 0))) return rc;
-  }
-  // ---- adjust decay: decay_params + decay_times of the equalized rows that have a target, the window in place
-  if (s->decay_on) {
-    const int64_t two_fs = (int64_t)(2 * s->fs);
-    const int64_t span_max = std::max<int64_t>(1, std::min(two_fs, s->out_len_max));
-    const int mean_pitch = imp::kKneeMaxWindows + 1;
-    hipLaunchKernelGGL(imp::slice_decay_rows_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, (const long long*)s->d_outlen, (int)R, (int)B,
-                       (long long)out_pitch, s->d_off3, s->d_len3);
-    hipLaunchKernelGGL(imp::row_chunk_max_kernel, dim3((unsigned)s->dchunks, (unsigned)B), dim3(256), 0, st, (const float*)d_out, s->d_off3, s->d_len3,
-                       (int64_t)0, s->d_dchunk, s->dchunks);
-    hipLaunchKernelGGL(imp::row_first_peak_chunked_kernel, dim3((unsigned)B), dim3(imp::kPeakThreads), 0, st, (const float*)d_out, s->d_off3, s->d_len3,
-                       (int64_t)0, (const unsigned*)nullptr, 0, (const unsigned*)s->d_dchunk, s->dchunks, s->d_res3, s->peak_height,
-                       (long long*)nullptr);
-    hipLaunchKernelGGL(imp::knee_span_kernel, dim3((unsigned)B), dim3(64), 0, st, (const imp::RowPeak*)s->d_res3, s->d_off3, s->d_len3,
-                       (long long)two_fs, s->fs, s->d_knee, s->d_max);
-    const int bpr = (int)std::max<int64_t>(1, std::min<int64_t>(64, (span_max + 8191) / 8192));
-    hipLaunchKernelGGL(imp::knee_maxabs_kernel, dim3((unsigned)bpr, (unsigned)B), dim3(256), 0, st, (const float*)d_out, (const imp::KneeRow*)s->d_knee, s->d_max);
-    hipLaunchKernelGGL(imp::knee_windows_kernel, dim3(imp::kKneeRound1, (unsigned)B), dim3(256), 0, st, (const imp::KneeRow*)s->d_knee, (const float*)d_out,
-                       (const unsigned long long*)s->d_max, s->d_means, mean_pitch, 1);
-    hipLaunchKernelGGL(imp::knee_stage1_kernel, dim3((unsigned)B), dim3(64), 0, st, s->d_knee, (const double*)s->d_means, mean_pitch, s->fs);
-    hipLaunchKernelGGL(imp::knee_windows_kernel, dim3(64, (unsigned)B), dim3(256), 0, st, (const imp::KneeRow*)s->d_knee, (const float*)d_out,
-                       (const unsigned long long*)s->d_max, s->d_means, mean_pitch, 0);
-    hipLaunchKernelGGL(imp::knee_stage2_kernel, dim3((unsigned)B), dim3(256), 0, st, s->d_knee, (const double*)s->d_means, mean_pitch, (const float*)d_out,
-                       (const unsigned long long*)s->d_max, s->fs);
-    hipLaunchKernelGGL(imp::slice_decay_jobs_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, (const imp::KneeRow*)s->d_knee,
-                       (const double*)s->d_target, (int)R, (int)B, (long long)s->dscratch, s->d_jobs);
-    hipLaunchKernelGGL(imp::decay_times_kernel<float>, dim3((unsigned)B), dim3(imp::kDecayThreads), 0, st, (const float*)d_out, (const imp::DecayJob*)s->d_jobs, s->d_dscr,
-                       s->fs, s->d_rt);
-    hipLaunchKernelGGL(imp::slice_decay_params_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, st, (const imp::KneeRow*)s->d_knee,
-                       (const double*)s->d_rt, (const double*)s->d_target, (const int64_t*)s->d_len3, (int)R, (int)M, s->fs, s->d_dlen, s->d_dpar,
-                       s->d_rows, s->d_flags);
-    hipLaunchKernelGGL(imp::apply_window_copy_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (s->out_len_max + 1023) / 1024)), (unsigned)B),
-                       dim3(256), 0, st, (const float*)d_out, (const int64_t*)s->d_off3, d_out, (const int64_t*)s->d_off3,
-                       (const int64_t*)s->d_dlen, (const imp::WindowParams*)s->d_dpar);
-    HIP_TRY(hipGetLastError());
-  }
-  // ---- normalize: maxima of the ear sums' spectra, gain on the device, applied in place
-  if ((rc = slice_norm_run(ctx, s->norm, d_out, out_pitch, (int)R, (const long long*)s->d_outlen, M, s->d_peak_db))) return rc;
-  hipLaunchKernelGGL(imp::slice_gain_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, st, (const double*)s->d_peak_db,
-                     (const long long*)s->d_outlen, (int)R, (int)M, s->peak_target, s->guard_rel, (long long)out_pitch, s->d_g_off, s->d_g_len,
-                     s->d_g_par, s->d_meas, s->d_flags);
-  hipLaunchKernelGGL(imp::apply_window_copy_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (s->out_len_max + 1023) / 1024)), (unsigned)B),
-                     dim3(256), 0, st, (const float*)d_out, (const int64_t*)s->d_g_off, d_out, (const int64_t*)s->d_g_off,
-                     (const int64_t*)s->d_g_len, (const imp::WindowParams*)s->d_g_par);
-  HIP_TRY(hipGetLastError());
+  if (s->decay_on && (rc = slice_decay(s, st, M, d_out, out_pitch))) return rc;
+  if ((rc = slice_normalize(s, st, M, d_out, out_pitch))) return rc;
   // ---- the scalars, once
+  const int64_t B = M * s->R;
   HIP_TRY(hipMemcpyAsync(s->h_rows, s->d_rows, (size_t)B * sizeof(imp::SliceRowOut), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(s->h_meas, s->d_meas, (size_t)M * sizeof(imp::SliceMeasOut), hipMemcpyDeviceToHost, st));
   s->last_M = M;

@@ -925,6 +925,48 @@ def test_alignment_and_shift_behaviour(gpu_ctx):
     assert len(x.data) == 4
 
 
+def test_window_and_shift_of_device_rows_across_the_grid_breaks(gpu_ctx):
+    """imp_apply_window_device and imp_shift_rows_device share one grid: a block per 1024 samples of the longest row, at
+    most 256 a row.  Rows of 1, 1023, 1024, 1025 samples and of 256 * 1024 + 1, the first length the cap binds at, in one
+    batch: the window exactly NumPy's slice-and-multiply, the shift exactly ImpulseResponse.shift, nothing written
+    between the rows."""
+    from impulse_hip.impulse_response import ImpulseResponse
+    rng = np.random.default_rng(31)
+    lens = np.array([1, 1023, 1024, 1025, 256 * 1024 + 1], dtype=np.int64)
+    gap = 3
+    offs = np.concatenate([[gap], gap + np.cumsum(lens + gap)[:-1]]).astype(np.int64)
+    flat = rng.standard_normal(int(offs[-1] + lens[-1] + gap)).astype(np.float32)
+    between = np.ones(len(flat), dtype=bool)
+    for o, n in zip(offs, lens):
+        between[o:o + n] = False
+    d_src, d_dst = gpu_ctx.malloc(flat.nbytes), gpu_ctx.malloc(flat.nbytes)
+    try:
+        gpu_ctx.h2d(d_src, flat)
+        out = np.empty_like(flat)
+        gains = np.array([0.5, -1.25, 0.3, 1.7, 0.9], dtype=np.float32)
+        gpu_ctx.memset(d_dst, 0xFF, flat.nbytes)
+        gpu_ctx.apply_window_device(d_src, offs, d_dst, offs, lens, [dict(gain=float(g)) for g in gains])
+        gpu_ctx.synchronize()
+        gpu_ctx.d2h(out, d_dst)
+        for o, n, g in zip(offs, lens, gains):
+            want = (flat[o:o + n].astype(np.float64) * np.float64(g)).astype(np.float32)
+            assert np.array_equal(out[o:o + n], want), int(n)
+        assert np.all(out.view(np.uint32)[between] == 0xFFFFFFFF)
+        shifts = np.array([0, 5, -1023, 1024, -100000], dtype=np.int64)
+        gpu_ctx.memset(d_dst, 0xFF, flat.nbytes)
+        gpu_ctx.shift_rows_device(d_src, offs, lens, shifts, d_dst, offs)
+        gpu_ctx.synchronize()
+        gpu_ctx.d2h(out, d_dst)
+        for o, n, sh in zip(offs, lens, shifts):
+            ir = ImpulseResponse(flat[o:o + n].astype(np.float64), 48000)
+            ir.shift(int(sh))
+            assert np.array_equal(out[o:o + n].astype(np.float64), ir.data), (int(n), int(sh))
+        assert np.all(out.view(np.uint32)[between] == 0xFFFFFFFF)
+    finally:
+        gpu_ctx.free(d_src)
+        gpu_ctx.free(d_dst)
+
+
 def test_overlapped_launch_groups_are_bit_identical(gpu_ctx):
     """imp_plan_set_overlap: launch groups on 3 lanes (private workspace slices, 3 streams) must give
     exactly the bytes of the strictly serial order, within one call and across calls."""
